@@ -9,6 +9,10 @@ A "step" = one full training step on one synthetic batch already resident in HBM
 multimodal BART-large forward (+ fused LM-head/CE), frozen guide BART forward, CoLaM + SECLA losses,
 backward, gradient all-reduce (N > 1), fused AdamW + LR schedule.  Nothing is skipped or cached.
 Prints ONE JSON line (rank 0).
+
+A plain run measures the headline figure only: set-up, warm-up, the K timed steps (the last one instrumented, see
+--no-roofline-step), the result line.  `--full` adds the measurements that take runs of their own: the target-GEMM, config-4
+and config-5 (caption generation) legs and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed.
 """
 import argparse
 import json
@@ -42,9 +46,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE: 32)")
     ap.add_argument("--seq", type=int, default=512, help="article tokens S")
     ap.add_argument("--cap", type=int, default=64, help="caption tokens T")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline figure, everything else the benchmark measures: the target-GEMM, "
+                    "config-4 and config-5 (caption generation) legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as float32 .npy files "
+                    "into DIR: its four losses and a fixed sample of every trainable weight it updated")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=2, help="batch of the CPU baseline legs (SURVEY §8d: 2)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the target-GEMM and config-5 (caption generation) legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the target-GEMM, config-4 and config-5 (caption generation) legs")
     ap.add_argument("--grad-transport", choices=("fp32", "bf16"), default="fp32",
                     help="N>1: dtype of the gradient all-reduce (fp32 = the reference's DDP; bf16 halves the xGMI volume)")
     ap.add_argument("--no-streams", action="store_true", help="single-stream schedule (no side streams for guide / wgrad)")
@@ -58,7 +66,10 @@ def parse():
     ap.add_argument("--no-roofline-step", action="store_true", help="A/B aid: every timed step runs in the launch mode under test (the last one "
                     "is normally an eager single-stream step with HIP events around every GEMM, the roofline measurement); the roofline object is then null")
     ap.add_argument("--mock-step", action="store_true", help=argparse.SUPPRESS)    # tests/test_bench_launch.py: launcher plumbing without a GPU
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 class GemmTimer:
@@ -401,6 +412,40 @@ def cfg4_leg(model, guide, opt, args, cfg, B, T, rank=0, steps=4):
             "loss_total": float(out4[0].item())}
 
 
+DUMP_PER_TENSOR = 4096      # elements sampled from each updated weight tensor by --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy, float32, 64 MB at most in all."""
+    import numpy as np
+    vals = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(v.nbytes for v in vals.values())
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {total / 1e6:.1f} MB, more than 64 MB")
+    os.makedirs(path, exist_ok=True)
+    for name, v in vals.items():
+        np.save(os.path.join(path, f"{name}.npy"), v)
+    log(f"outputs of the last timed step -> {path} ({', '.join(vals)}; {total / 1e6:.1f} MB)")
+
+
+def step_outputs(out4, model):
+    """What one training step hands back and leaves behind: its losses [total, txt, secla, colam] and the fp32 master weights
+    AdamW just updated, DUMP_PER_TENSOR elements of every trainable tensor (all of a smaller one) in name order, at positions
+    drawn from a generator seeded by the tensor's name, so that two builds sample the same elements."""
+    import zlib
+    parts = []
+    for name, p in sorted(model.named_parameters()):
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_TENSOR:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, flat.numel(), (DUMP_PER_TENSOR,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float())
+    return {"losses": out4, "weights_sample": torch.cat(parts)}
+
+
 def mock_main(a):
     """`--mock-step`: the launcher / rendezvous / reporting plumbing of the N > 1 path with the training step replaced by a
     sleep + one small all-reduce on CPU tensors (gloo) — what tests/test_bench_launch.py drives without a GPU.  Same JSON
@@ -429,6 +474,8 @@ def mock_main(a):
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"allreduced": g})
     if rank == 0:
         print(json.dumps({"metric": "mock", "value": round(a.batch * world * a.steps / dt, 2), "unit": "samples/s", "n_gpus": world,
                           "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
@@ -509,7 +556,12 @@ def main():
     cfg, vcfg = bart_large_vit_l14()
     B, S, T = a.batch, a.seq, a.cap
     log("building models (random init on device)")
-    model, guide, _ = build_models(cfg, vcfg, device="cuda", seed=1234, init="device")
+    # the modules are constructed on the GPU: their constructors' own random init (1.6 G parameters, some 20 s on the host) is
+    # overwritten by build_models' seeded device init anyway, and the step draws nothing from torch's global generators.  The
+    # constructors' tensors, copied into the arenas, are handed back to the device.
+    with torch.device("cuda"):
+        model, guide, _ = build_models(cfg, vcfg, device="cuda", seed=1234, init="device")
+    torch.cuda.empty_cache()
     log(f"models ready: {model.arena.n/1e6:.1f}M trainable, {guide.arena.n/1e6:.1f}M guide, {model.clip_model.visual.arena.n/1e6:.1f}M ViT")
     args = TrainArgs(num_training_steps=100000)
     opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay,
@@ -645,6 +697,8 @@ def main():
         dt = t.item()
     losses = out4.tolist()
     log(f"timed {a.steps} steps in {dt:.3f}s (host enqueue {host_dt / a.steps * 1e3:.1f} ms/step); losses {losses}")
+    if rank == 0 and a.dump_outputs:        # before the --full legs, which train the model further
+        dump_outputs(a.dump_outputs, step_outputs(out4, model))
     if rank == 0:
         agg = timer.summary()
         dom = max(agg.items(), key=lambda kv: kv[1][1]) if agg else None
@@ -716,7 +770,7 @@ def main():
                "step_mfma_frac": round(value / world * gf / 1e3 / PEAK_BF16_TFLOPS, 4) if gf else None,
                "losses_last_step": {"total": losses[0], "txt": losses[1], "secla": losses[2], "colam": losses[3]},
                "roofline": roof}
-        if world == 1 and not a.no_extras and not force_ddp:
+        if a.full and world == 1 and not a.no_extras and not force_ddp:
             try:
                 res["target_gemm"] = target_gemm_leg()
                 res["extra"] = {"config5_generation": decode_leg(model, cfg)}
@@ -727,7 +781,7 @@ def main():
                 res["extra"]["cfg4_step"] = cfg4_leg(model, guide, opt, args, cfg, B, T)
             except Exception as e:
                 res["extra"]["cfg4_step"] = {"error": repr(e)}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 log("cpu baseline (oracle on host cores)")
                 res["cpu_baseline"] = cpu_baseline(a.cpu_batch, S, T)

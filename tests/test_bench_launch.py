@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra_env=None, gpus=2):
+def _run(extra_env=None, gpus=2, extra_args=()):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env or {})
     # the parent must not make a GPU call: poison torch.cuda's lazy initialisation in THIS interpreter only (sitecustomize-style
@@ -20,7 +20,7 @@ def _run(extra_env=None, gpus=2):
         "import sys, os, runpy, torch\n"
         "def _boom(*a, **k): raise RuntimeError('parent process touched the GPU')\n"
         "torch.cuda._lazy_init = _boom; torch.cuda.set_device = _boom; torch.cuda.init = _boom\n"
-        f"sys.argv = ['bench.py', '--gpus', '{gpus}', '--steps', '5', '--warmup', '1', '--mock-step']\n"
+        f"sys.argv = ['bench.py', '--gpus', '{gpus}', '--steps', '5', '--warmup', '1', '--mock-step'] + {list(extra_args)!r}\n"
         f"runpy.run_path({os.path.join(ROOT, 'bench.py')!r}, run_name='__main__')\n")
     return subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
 
@@ -56,3 +56,22 @@ def test_bench_under_an_external_launcher_does_not_relaunch():
     recs = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(recs) == 1 and recs[0]["world_size_reported"] == 2
     assert "launching" not in r.stderr
+
+
+def test_bench_full_and_dump_outputs_flags(tmp_path):
+    """`--full` is accepted and `--dump-outputs DIR` leaves float32 .npy files of the last step's results (rank 0 only)."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    r = _run(extra_args=("--full", "--dump-outputs", str(out)))
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    recs = [json.loads(ln) for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(recs) == 1 and recs[0]["steps"] == 5 and recs[0]["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["allreduced.npy"]
+    v = np.load(out / "allreduced.npy")
+    assert v.dtype == np.float32 and v.shape == (1024,) and np.allclose(v, 1.0)
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--mock-step"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode != 0 and "--steps" in r.stderr
