@@ -90,7 +90,7 @@ def _worker(rank, world, port, q):
         # passes.  Round 3 had to gate (ii) at 5e-2: the LM-head dgrad summed its vocabulary chunks with split-K fp32 atomics whose
         # order varied when two processes shared the card, one bf16 element of dH rounded the other way about every second pass,
         # and AdamW's first step (sign(g) lr) turned that into 1-2 % of the update's norm.  The dgrad now sums through the GEMM's
-        # ordered fix-up (ops.LMHEAD_FIXUP): what is left are the LayerNorm-parameter atomics (1e-7), and the gate is 1e-4 again.
+        # ordered fix-up (ops.LmHeadCeFn): what is left are the LayerNorm-parameter atomics (1e-7), and the gate is 1e-4 again.
         from vacnic_amd.training import FusedAdamW, train_step
         w = ddp.DistributedDataParallel(model, bucket_bytes=8 << 20)
         opt = FusedAdamW(model.arena, lr=1e-3, num_warmup_steps=0, num_training_steps=10, world_size=world)

@@ -18,19 +18,7 @@ rm -f gpurun_out/_ab_line.txt
 if [ "$2" = "split" ]; then
 for rep in 1 2; do
   run "hybrid (default)" VACNIC_WGRAD_GROUP=1
-  run "hybrid, split-K factors x2" VACNIC_WGRAD_SPLIT_SCALE=2
-  run "hybrid, split-K factors x0.5" VACNIC_WGRAD_SPLIT_SCALE=0.5
   run "hybrid, no measured tile table" VACNIC_GEMM_TUNED=0
-done
-exit 0
-fi
-if [ "$2" = "prio" ]; then
-python -c "import torch; print('priority range', torch.cuda.Stream.priority_range())" | tee -a $out
-for rep in 1 2; do
-  run "default priorities" VACNIC_WGRAD_GROUP=1
-  run "no branch stream (encoder branches on the compute stream)" VACNIC_NO_BRANCH_STREAM=1
-  run "no weight-gradient stream" VACNIC_NO_WGRAD_STREAM=1
-  run "two tower streams" VACNIC_TWO_TOWER_STREAMS=1
 done
 exit 0
 fi
@@ -45,9 +33,7 @@ done
 exit 0
 fi
 for rep in 1 2; do
-  run "grouped everything, 4096-row phases" VACNIC_WGRAD_GROUP_MAX_M=1000000 VACNIC_WGRAD_PHASE_ROWS=4096
-  run "grouped everything, 2048-row phases" VACNIC_WGRAD_GROUP_MAX_M=1000000 VACNIC_WGRAD_PHASE_ROWS=2048
-  run "grouped everything, whole reduction per launch" VACNIC_WGRAD_GROUP_MAX_M=1000000
+  run "grouped everything" VACNIC_WGRAD_GROUP_MAX_M=1000000
   run "split-K with fp32 atomics (round 2)" VACNIC_WGRAD_GROUP=0
   run "hybrid: grouped for M<=4096, split-K above (default)" VACNIC_WGRAD_GROUP=1
 done

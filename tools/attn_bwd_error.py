@@ -34,5 +34,5 @@ for name, Tq, Tk, causal in (("decoder self (64 x 64, causal)", 64, 64, True), (
                              ("encoder self (512 x 512)", 512, 512, False)):
     for sc, cm in ((1.0, 0.0), (0.2, 0.0), (0.2, 1.0), (0.2, 3.0)):
         e = run(4, 16, Tq, Tk, sc, causal, cm)
-        print(f"[VACNIC_ATTN_DELTA={os.environ.get('VACNIC_ATTN_DELTA', '0')}] {name:32s} q,k std {sc:4.2f} common component {cm:3.1f}: "
+        print(f"{name:32s} q,k std {sc:4.2f} common component {cm:3.1f}: "
               f"rel err dq {e[0]:.4f} dk {e[1]:.4f} dv {e[2]:.4f}", flush=True)

@@ -24,8 +24,6 @@ def spy(self, *a):
     o = orig(self, *a); torch.cuda.synchronize(); encs.append(o.float().clone()); return o
 Gn.GraphedCall.__call__ = spy
 gold = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "generate_cfg5_m4.npz"))
-if len(sys.argv) > 1:
-    K._FIX_CAPTURE_FLOOR = int(sys.argv[1]) << 20
 for name, extra in F5.CASES:
     want = torch.from_numpy(gold[name])
     for leg in ("eager", "capture", "replay", "host"):

@@ -903,12 +903,8 @@ extern "C" int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream) {
   const size_t lds_q = 4 * TILE_B + Tk_pad * 4 + (Tk_pad >> 6) * 4;
   p.delta_out = a->delta;
   // delta: from the kernels' own P and dP (a sweep of the dQ kernel without its last product) for the decoder-sized problems,
-  // where it costs microseconds; rowsum(dO o O) for the long encoder sequences (a_delta_mode: 0 = by size, 1 = always the sweep,
-  // 2 = always rowsum(dO o O))
-  static int env_mode = -1;
-  if (env_mode < 0) { const char* e = getenv("VACNIC_ATTN_DELTA"); env_mode = e ? atoi(e) : 0; }
-  const bool sweep = env_mode == 1 || (env_mode == 0 && p.Tq <= 128);
-  if (sweep) {
+  // where it costs microseconds; rowsum(dO o O) for the long encoder sequences
+  if (p.Tq <= 128) {
     if (p.drop_thr) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), lds_q, s, p);
     else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), lds_q, s, p);
   } else {

@@ -785,8 +785,6 @@ static int lt_tiles_per_wg(int64_t V) {
   const int64_t nt = (V + 15) / 16;
   int64_t tpw = (nt + 511) / 512;                  // at most 512 workgroups (two per CU), all of them with the same number of tiles
   if (tpw < 1) tpw = 1;
-  static const char* dbg = getenv("VACNIC_LT_TPW");    // measurement aid (tools/bench_lmhead_topk.py): tiles per workgroup, >= the default
-  if (dbg && atoi(dbg) >= tpw && atoi(dbg) * 16 <= LT_MAXCOLS) tpw = atoi(dbg);
   return (int)tpw;
 }
 

@@ -928,10 +928,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
 // re-read by its 8 consumers from that XCD's L2 — the traffic of the K-slice-per-XCD split-K mapping without its fp32
 // atomics (32 MB of memory-side atomics for a 1024 x 1024 gradient at split 8: ~25 of the launch's 60 us), and the sums are
 // bitwise reproducible: every output element has ONE writer and a fixed summation order.
-// Optionally (VACNIC_WGRAD_PHASE_ROWS) a long reduction is cut into PHASES, one launch each over the same grid (dW read-modify-
-// written once per phase): shorter-lived workgroups.  Measured, it does not change how the encoder-sized groups delay the compute
-// stream's chain (67.4 vs 67.4 ms/step at 4096 rows, 68.5 at 2048: profiles/r3_step_ab_wgrad.txt), so it is off by default; what
-// the step time wants is decided in ops._groupable (only reductions of <= 4096 rows are grouped).
+// The kernel can reduce one PHASE of the rows per launch (dW read-modify-written once per phase: shorter-lived workgroups); the host
+// launches the whole reduction as one phase.  Cutting it into 4096- or 2048-row phases did not change how the encoder-sized groups
+// delay the compute stream's chain (67.4 vs 67.4 ms/step at 4096 rows, 68.5 at 2048: profiles/r3_step_ab_wgrad.txt); what the step
+// time wants is decided in ops._groupable (only reductions of <= 4096 rows are grouped).
 constexpr int GROUP_UT = 8;                 // tiles per unit side (128-wide tiles: 1024 x 1024 outputs per unit)
 constexpr int GROUP_MAX_UNITS = 16;
 struct GroupUnit {

@@ -344,15 +344,14 @@ __global__ __launch_bounds__(256) void zero_words_kernel(unsigned* __restrict__ 
 }  // namespace
 
 // zero-fill on the caller's stream — the fp32 accumulators of split-K GEMMs, the arrival counters of the split-K fix-up.  A memset
-// (no kernel) on an ordinary stream; while the stream is being CAPTURED into a hipGraph a fill kernel instead (VACNIC_ZERO_MEMSET_IN_GRAPHS=1
-// keeps the memset node): see DESIGN section 0, item 5 (c).
+// (no kernel) on an ordinary stream; while the stream is being CAPTURED into a hipGraph a fill kernel instead (a memset node was
+// not ordered before the next kernel node): see DESIGN section 0, item 5 (c).
 extern "C" int vacnic_zero_bytes(void* ptr, int64_t bytes, void* stream) {
   VPLAN_REC(vacnic_zero_bytes, ptr, bytes, stream);
   VCHECK(ptr && bytes >= 0, VACNIC_BAD_SHAPE, "zero_bytes: bad operand");
   if (bytes == 0) return VACNIC_OK;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  static const bool memset_in_graphs = getenv("VACNIC_ZERO_MEMSET_IN_GRAPHS") && atoi(getenv("VACNIC_ZERO_MEMSET_IN_GRAPHS"));
-  if (!memset_in_graphs && (((uintptr_t)ptr | (uintptr_t)bytes) & 3) == 0 && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess &&
+  if ((((uintptr_t)ptr | (uintptr_t)bytes) & 3) == 0 && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess &&
       cs == hipStreamCaptureStatusActive) {
     const long n = (long)(bytes >> 2);
     long nb = (n + 255) / 256;

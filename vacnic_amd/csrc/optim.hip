@@ -134,7 +134,6 @@ extern "C" int vacnic_adamw(const vacnic_adamw_args* a, void* stream) {
   const long n4 = a->n >> 2;
   unsigned blocks = 65536;                     // wide launch (see the kernel comment); small arenas: one element per thread
   const long need = (n4 + 255) / 256;
-  if (const char* e = getenv("VACNIC_ADAMW_BLOCKS")) { const long bb = atol(e); if (bb > 0) blocks = (unsigned)bb; }   // A/B knob
   if (need < blocks) blocks = (unsigned)(need < 1 ? 1 : need);
   hipLaunchKernelGGL(adamw_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
                      (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->weight_decay, a->grad_scale, a->zero_grad,

@@ -153,10 +153,8 @@ _load_tuned()
 
 
 _SMALLM_SPLIT = __import__("os").environ.get("VACNIC_SMALLM_SPLIT", "0") != "0"      # 1: K slices for the batch-1 fc2 GEMMs of the encoder / ViT (off: see DESIGN section 0, item 5 (c))
-_TUNED_FIXUP = __import__("os").environ.get("VACNIC_GEMM_FIXUP_TUNED", "1") != "0"      # A/B: 0 = ignore the fix-up entries of gemm_tuned.json
 _FIX = {}                 # launch stream -> [workspace (uint8), counters (int32, all zero between launches)]
 _FIX_CAPTURE = {}         # the same for launches recorded by a hipGraph capture on that stream (buffers from the graph's private pool)
-_FIX_CAPTURE_FLOOR = 0    # bytes (a debugging aid: tools/enc_graph_check.py)
 _CAPTURE_SCOPE = 0        # owner of the graph being captured (capture_scope); 0: graphs that replay in order on one stream
 _FIX_OLD = []             # outgrown workspaces: kernels already enqueued may still use them
 
@@ -190,7 +188,7 @@ def _fix_buffers(stream, M, N, split_k):
     key = (stream, _CAPTURE_SCOPE) if capturing else stream
     ent = table.get(key)
     if ent is None or ent[0].numel() < need or ent[1].numel() < ncnt:
-        floor = _FIX_CAPTURE_FLOOR if table is _FIX_CAPTURE else 64 << 20
+        floor = 0 if capturing else 64 << 20
         ws = torch.empty(max(need, ent[0].numel() if ent else 0, floor), device="cuda", dtype=torch.uint8)
         cnt = torch.empty(max(ncnt, ent[1].numel() if ent else 0, 4096), device="cuda", dtype=torch.int32)
         call("vacnic_zero_bytes", cnt.data_ptr(), cnt.numel() * 4, stream)
@@ -220,12 +218,12 @@ def gemm(x, w, M, N, K, *, bias=None, out=None, ldx=None, ldw=None, ldo=None, x_
         if t is not None and len(t) > 4 and t[4]:
             # measured winner = K slices through the ordered fix-up (long reductions into a small output: too few tiles to fill
             # 256 CUs unsplit, and a bf16 / activation / residual epilogue cannot meet in atomics)
-            if _TUNED_FIXUP and split_k == 1:
+            if split_k == 1:
                 tile_hint, split_k, fixup = t[0], t[1], True
         elif t is not None:
             tile_hint = t[0] or -1
             if out_mode == 2:
-                split_k = t[1] if _SPLIT_SCALE == 1.0 else max(1, min(32, int(t[1] * _SPLIT_SCALE)))
+                split_k = t[1]
         elif (t is None and _SMALLM_SPLIT and split_k == 1 and not fixup and 8 < M <= 1024 and K >= 4096 and N <= 2048 and out_mode != 2
               and xsum is None and not x_kstrided and not w_kstrided and not torch.is_grad_enabled()):
             # one caption's encoder / ViT pass (batch 1: M = 512 tokens, 257 patches), fc2: 64 x 128 tiles give <= 64 workgroups, each
@@ -263,18 +261,11 @@ def gemv_ln(x, residual, gamma, beta, w, M, N, Kd, *, bias=None, out=None, ln_ou
     return out
 
 
-_SPLIT_SCALE = float(__import__("os").environ.get("VACNIC_WGRAD_SPLIT_SCALE", "1"))     # A/B aid: finer / coarser K slices in the step
-
-
 def wgrad_split(M_red, n_tiles):
     """split-K factor for a weight gradient whose reduction runs over M_red rows: aim at >= 512 workgroups."""
     s = 1
     while n_tiles * s < 512 and M_red // (s * 2) >= 512 and s < 16:
         s *= 2
-    if _SPLIT_SCALE != 1.0:
-        s = max(1, min(32, int(s * _SPLIT_SCALE)))
-        while s > 1 and M_red // s < 256:
-            s //= 2
     return s
 
 
@@ -317,8 +308,6 @@ def attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, key_mask=None, c
 
 
 # -------------------------------------------------------------------------------------------- LN family
-LN_TWO_STAGE = __import__("os").environ.get("VACNIC_LN_ATOMICS") != "1"     # A/B: VACNIC_LN_ATOMICS=1 = round-1 per-column atomics
-
 def add_ln_fwd(x, residual, gamma, beta, eps=1e-5, p_drop=0.0, seed=0, need_stats=True, seed_dev=None):
     D = x.shape[-1]
     R = x.numel() // D
@@ -343,7 +332,7 @@ def add_ln_bwd(dout, x, residual, gamma, mean, rstd, dgamma, dbeta, p_drop=0.0, 
     else:
         dres = None            # identical to dx: caller reuses dx
     part, prow = None, 0
-    if LN_TWO_STAGE and dgamma is not None and R >= 256:
+    if dgamma is not None and R >= 256:         # two-stage dgamma / dbeta reduction (below 256 rows: per-column atomics)
         prow = min(1024, (R + 3) // 4)
         part = torch.empty((prow, 2, D), device=x.device, dtype=torch.float32)     # scratch of the two-stage dgamma/dbeta fold
     defer = fold_on is not None and part is not None and fold_on != _stream()

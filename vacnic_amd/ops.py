@@ -19,9 +19,6 @@ from . import kernels as K
 from . import streams
 
 BF16 = torch.bfloat16
-_NO_XSUM = __import__("os").environ.get("VACNIC_NO_XSUM") == "1"
-_LN_FOLD_ON_SIDE = __import__("os").environ.get("VACNIC_LN_FOLD_MAIN") != "1"      # A/B: 1 = the fold stays in the backward chain
-_FUSE_ACT_DROPOUT = __import__("os").environ.get("VACNIC_FUSE_ACT_DROPOUT", "1") != "0"      # A/B: 0 = separate in-place dropout passes
 
 
 class Rng:
@@ -77,9 +74,9 @@ def _c(t):
 
 
 def _bw(fn):
-    """decorator of Function.backward: launch on the HIP stream the op's forward was launched on (ctx.raw, set by _tag).  With
-    explicit scheduling torch sees one stream, so the autograd engine no longer puts a node's backward on its forward's stream
-    (nor synchronises around it: the fences are ours, StreamHopFn)."""
+    """decorator of Function.backward: launch on the HIP stream the op's forward was launched on (ctx.raw, set by _tag).  Torch
+    sees one stream (side-stream work goes through kernels.launch_on), so the autograd engine does not put a node's backward on
+    its forward's stream, nor synchronise around it: the fences are ours (StreamHopFn)."""
     def backward(ctx, *grads):
         raw = getattr(ctx, "raw", None)
         if raw is None or raw == K._OVERRIDE:
@@ -100,8 +97,7 @@ def _tag(ctx):
 class StreamHopFn(Function):
     """identity on tensors that cross from HIP stream `src` (where they were produced) to stream `dst` (where they are consumed):
     forward = fence(src -> dst); backward = fence(dst -> src), issued by the autograd engine exactly when all the gradients of the
-    crossing tensors have been enqueued on dst.  The explicit counterpart of what the engine does implicitly for ops run under
-    torch.cuda.stream()."""
+    crossing tensors have been enqueued on dst."""
 
     @staticmethod
     def forward(ctx, src, dst, *xs):
@@ -185,17 +181,10 @@ class _WgradQueue:
             for _, _, sp in jobs:
                 ddp.done(sp.wgrad, sp.bgrad)
             return
-        # (the side stream already waits for every queued job's producer: add() is called behind a producer -> side fence)
-        if ddp.TRACKER is None or streams.explicit():
-            with K.launch_on(streams.wgrad_raw(), fence=False):      # (every job fenced its producer -> wgrad stream when it was queued)
-                K.wgrad_group(packed)
-            for _, _, sp in jobs:
-                ddp.done(sp.wgrad, sp.bgrad)
-        else:
-            with torch.cuda.stream(side):
-                K.wgrad_group(packed)
-                for _, _, sp in jobs:
-                    ddp.done(sp.wgrad, sp.bgrad)
+        with K.launch_on(streams.wgrad_raw(), fence=False):      # (every job fenced its producer -> wgrad stream when it was queued)
+            K.wgrad_group(packed)
+        for _, _, sp in jobs:
+            ddp.done(sp.wgrad, sp.bgrad)
         for dy, x, _ in jobs:
             streams.keep(dy, x)
 
@@ -232,7 +221,7 @@ def begin_step():
 
 
 def _groupable(dy2d, x2d, spec, M):
-    return (WGRAD_GROUP and spec.wgrad is not None and not _NO_XSUM and WGRAD_GROUP_MIN_M <= M <= WGRAD_GROUP_MAX_M and spec.N >= 512 and spec.K >= 512
+    return (WGRAD_GROUP and spec.wgrad is not None and WGRAD_GROUP_MIN_M <= M <= WGRAD_GROUP_MAX_M and spec.N >= 512 and spec.K >= 512
             and dy2d.stride(0) % 8 == 0 and x2d.stride(0) % 8 == 0 and spec.wgrad.stride(0) % 4 == 0
             and dy2d.shape[1] == spec.N and x2d.shape[1] == spec.K)
 
@@ -249,55 +238,38 @@ def _wgrad(dy2d, x2d, spec, M):
         _wgrad_impl(dy2d, x2d, spec, M)
         ddp.done(spec.wgrad, spec.bgrad)
         return
-    if streams.explicit():
-        K.fence(K._stream(), streams.wgrad_raw())          # dy / x were produced on the stream this backward node launches on
-    else:
-        side.wait_stream(torch.cuda.current_stream())      # dy / x were produced on the compute stream
+    K.fence(K._stream(), streams.wgrad_raw())              # dy / x were produced on the stream this backward node launches on
     if group:
         _WGQ.add(dy2d, x2d, spec, M)
         return
-    if ddp.TRACKER is None or streams.explicit():
-        with K.launch_on(streams.wgrad_raw(), fence=False):
-            _wgrad_impl(dy2d, x2d, spec, M)
-        ddp.done(spec.wgrad, spec.bgrad)
-    else:
-        with torch.cuda.stream(side):                      # the bucket launcher reads torch's current stream
-            _wgrad_impl(dy2d, x2d, spec, M)
-            ddp.done(spec.wgrad, spec.bgrad)
+    with K.launch_on(streams.wgrad_raw(), fence=False):
+        _wgrad_impl(dy2d, x2d, spec, M)
+    ddp.done(spec.wgrad, spec.bgrad)
     streams.keep(dy2d, x2d)                                # alive until the compute stream joins the side stream
 
 
-# split-K weight gradients through the GEMM's ordered fix-up instead of fp32 atomics (bitwise reproducible dW):
-#   0 = atomics (rounds 1-3); 1 = fix-up with the same 128 x 128 tiles and split factors; 2 = fix-up, 256 x 256 tiles x 4 slices for
-#   outputs larger than 1024 x 1024 (the isolated winners of profiles/r4_gemm_fixup_vs_shipped.txt)
-# Default 2: same-box A/B 66.79 vs 67.16 ms/step (4 of 4 interleaved runs, profiles/r4_step_ab_fixup.txt) — and with it no weight
-# gradient is summed through atomics any more (the decoder-sized ones go through the grouped kernel): dW is bitwise reproducible.
-WGRAD_FIXUP = int(__import__("os").environ.get("VACNIC_WGRAD_FIXUP", "2"))
-
-
 def _wgrad_impl(dy2d, x2d, spec, M):
-    if spec.wgrad is not None and not _NO_XSUM:
-        N, Kd = spec.N, spec.K
-        tiles = ((N + 127) // 128) * ((Kd + 127) // 128)
-        split = K.wgrad_split(M, tiles)
-        if WGRAD_FIXUP and split > 1 and M >= 4096:
-            hint = 128
-            if WGRAD_FIXUP == 2 and N >= 512 and Kd >= 512:
-                hint, split = (128, 8) if N * Kd <= (1 << 20) else (256, 4)
-            K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
-                   x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad, fixup=True, tile_hint=hint)
-            return
-        # the bias gradient (column sums of dY) rides on the weight-gradient GEMM's own dY fragments (xsum): no second pass
-        K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
-               x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad)
-    else:
-        if spec.wgrad is not None:                  # A/B: VACNIC_NO_XSUM=1 restores the separate bias-gradient reduction
-            N, Kd = spec.N, spec.K
-            tiles = ((N + 127) // 128) * ((Kd + 127) // 128)
-            K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
-                   x_kstrided=True, w_kstrided=True, out_mode=2, split_k=K.wgrad_split(M, tiles))
+    if spec.wgrad is None:                          # a bias without a weight: a column-sum reduction of its own
         if spec.bgrad is not None:
             K.bias_grad(dy2d, spec.bgrad, M, spec.N)
+        return
+    N, Kd = spec.N, spec.K
+    tiles = ((N + 127) // 128) * ((Kd + 127) // 128)
+    split = K.wgrad_split(M, tiles)
+    # the bias gradient (column sums of dY) rides on the weight-gradient GEMM's own dY fragments (xsum): no second pass
+    if split > 1 and M >= 4096:
+        # split-K through the GEMM's ordered fix-up instead of fp32 atomics (bitwise reproducible dW); 256 x 256 tiles x 4 slices
+        # for outputs larger than 1024 x 1024 (the isolated winners of profiles/r4_gemm_fixup_vs_shipped.txt).  Same-box A/B
+        # 66.79 vs 67.16 ms/step against atomics (profiles/r4_step_ab_fixup.txt); the decoder-sized weight gradients go through
+        # the grouped kernel, so no weight gradient is summed through atomics
+        hint = 128
+        if N >= 512 and Kd >= 512:
+            hint, split = (128, 8) if N * Kd <= (1 << 20) else (256, 4)
+        K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
+               x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad, fixup=True, tile_hint=hint)
+        return
+    K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
+           x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad)
 
 
 # ------------------------------------------------------------------------------------------- Linear
@@ -369,7 +341,7 @@ class Mlp2Fn(Function):
         u = torch.empty((M, s1.N), device=x.device, dtype=BF16) if need else None
         h = torch.empty((M, s1.N), device=x.device, dtype=BF16)
         # activation dropout rides in the epilogue (after the activation); widths that are not multiples of 16: a separate pass
-        fuse = p_act > 0.0 and K.can_fuse_dropout(s1.N) and _FUSE_ACT_DROPOUT
+        fuse = p_act > 0.0 and K.can_fuse_dropout(s1.N)
         K.gemm(x2, s1.w16, M, s1.N, s1.K, bias=s1.bias, out=h, ldw=s1.ldw, act=act, preact=u,
                drop=(p_act, seed, Rng.device_counter()) if fuse else None)
         if p_act > 0.0 and not fuse:
@@ -395,7 +367,7 @@ class Mlp2Fn(Function):
         if s2.N % 8:                                   # 20-wide name-prefix output: give the GEMMs 16-byte rows
             dy2 = K.pad_cols(dy2, (s2.N + 7) // 8 * 8)
         du = torch.empty((M, s1.N), device=dy.device, dtype=BF16)
-        fuse = ctx.p_act > 0.0 and K.can_fuse_dropout(s1.N) and _FUSE_ACT_DROPOUT
+        fuse = ctx.p_act > 0.0 and K.can_fuse_dropout(s1.N)
         K.gemm(dy2, s2.w16, M, s1.N, s2.N, out=du, ldx=dy2.stride(0), ldw=s2.ldw, w_kstrided=True, act=act, dact_src=u,
                drop=(ctx.p_act, ctx.seed, Rng.device_counter()) if fuse else None)
         if ctx.p_act > 0.0 and not fuse:               # the mask commutes with the elementwise act'(u) the epilogue applied
@@ -641,7 +613,7 @@ class AddLnFn(Function):
         x, res, mean, rstd = ctx.saved_tensors
         gamma, beta = ctx.gb
         # the fold of the LayerNorm parameter gradients (needed by AdamW / the reducer only) rides on the weight-gradient stream
-        side = streams.wgrad_raw() if (streams.explicit() and streams.wgrad_stream() is not None and _LN_FOLD_ON_SIDE) else None
+        side = streams.wgrad_raw() if streams.wgrad_stream() is not None else None
         dx, dres = K.add_ln_bwd(_c(dout), x, res, gamma, mean, rstd, gamma.grad, beta.grad, p_drop=ctx.p, seed=ctx.seed,
                                 seed_dev=Rng.device_counter() if ctx.p > 0 else None,
                                 need_dres=ctx.has_res and ctx.needs_input_grad[1], fold_on=side)
@@ -671,7 +643,7 @@ class EmbedLnFn(Function):
     def backward(ctx, dout):
         ids, mean, rstd = ctx.saved_tensors
         tok, pos, gamma, beta, scale, p, seed, pad = ctx.args
-        if streams.explicit() and streams.wgrad_stream() is not None:
+        if streams.wgrad_stream() is not None:
             # the tied matrix has another writer on the weight-gradient stream (the LM head's dE GEMMs: plain read-modify-write of
             # the same rows this kernel adds to with atomics): order behind it
             K.fence(streams.wgrad_raw(), K._stream())
@@ -762,8 +734,7 @@ LMHEAD_CHUNK = 16384        # vocabulary columns of dlogits alive at a time in t
 # GEMM's ordered fix-up (workspace + arrival tickets, include/vacnic_hip.h) — bitwise reproducible at the speed of the fp32
 # atomics it replaces (R = 2048: 89.7 vs 88.0 us per chunk, profiles/r4_gemm_fixup_vs_shipped.txt).  With atomics the summation
 # order varied whenever a second process shared the GPU, one bf16 element of dh rounded the other way about every second pass,
-# and backward amplified that to 1e-5 .. 2e-3 on every gradient (tools/grad_determinism.py).  VACNIC_LMHEAD_ATOMICS=1: round 3.
-LMHEAD_FIXUP = __import__("os").environ.get("VACNIC_LMHEAD_ATOMICS") != "1"
+# and backward amplified that to 1e-5 .. 2e-3 on every gradient (tools/grad_determinism.py).
 
 
 class LmHeadCeFn(Function):
@@ -796,7 +767,7 @@ class LmHeadCeFn(Function):
         # dE (the tied matrix's weight gradient) is needed only by AdamW / the reducer: with side streams on it runs on the
         # weight-gradient stream beside the next chunk's dlogits / dh GEMMs, out of the decoder phase's chain (the least busy part of
         # the step).  Two dlogits buffers alternate; a chunk's buffer is reused only after the side stream has read it.
-        side = streams.wgrad_stream() if (egrad is not None and streams.explicit()) else None
+        side = streams.wgrad_stream() if egrad is not None else None
         dls = [torch.empty((R, CH), device=h2.device, dtype=BF16) for _ in range(2 if side is not None else 1)]
         dh32 = K.zero_(torch.empty((R, d), device=h2.device, dtype=torch.float32))
         for ci, c0 in enumerate(range(0, V, CH)):
@@ -808,10 +779,7 @@ class LmHeadCeFn(Function):
             K.lmhead_ce_dlogits(h2, emb16_pad, tgt, V, rowp, dl, c0, n, ignore_index=ignore_index)
             ec = emb16_pad[c0:c0 + n8]
             # dh += dlogits_c . E_c: a reduction 8-16x longer than the output is wide -> split-K, fp32 accumulate
-            if LMHEAD_FIXUP:
-                K.gemm(dl, ec, R, d, n8, out=dh32, ldx=CH, w_kstrided=True, out_mode=2, split_k=4, fixup=True, tile_hint=128)
-            else:
-                K.gemm(dl, ec, R, d, n8, out=dh32, ldx=CH, w_kstrided=True, out_mode=2, split_k=8)
+            K.gemm(dl, ec, R, d, n8, out=dh32, ldx=CH, w_kstrided=True, out_mode=2, split_k=4, fixup=True, tile_hint=128)
             if egrad is not None:                                  # dE[c0:c0+n] += dlogits_c^T h
                 tiles = ((n + 127) // 128) * ((d + 127) // 128)
                 if side is not None:

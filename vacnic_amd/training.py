@@ -182,10 +182,10 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
         img_cls, gh = towers.img_cls, towers.gh
         for tns in (src_mask, tgt_mask, tgt_in):
             tns.record_stream(main)
-    elif streams.explicit():
-        # explicit scheduling (see streams.explicit): the same schedule as the branch below — id preprocessing + frozen guide
-        # forward on the aux stream, frozen ViT on its own stream — with kernels.launch_on / kernels.fence instead of
-        # torch.cuda.stream contexts and Tensor.record_stream, so that the whole step can be recorded into a launch plan
+    else:
+        # id preprocessing + frozen guide forward + frozen ViT on the side streams: they depend only on the batch, so they fill
+        # the bubbles of the main chain (and of the previous step's AdamW); launched through kernels.launch_on and ordered by
+        # kernels.fence, so that the whole step can be recorded into a launch plan (see streams)
         main_raw, aux_raw, vis_raw = K._stream(), streams.raw("aux"), streams.raw("vit")
         if ready is None:
             K.fence(main_raw, aux_raw)
@@ -199,34 +199,10 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
         K.fence(aux_raw, main_raw)              # the student needs the masks now, the guide's output only at the CoLaM loss
         with K.launch_on(vis_raw):              # the student's encoder input needs the image feature: ViT goes first
             img_cls = extract_clip_img_feat(net.clip_model, batch["img_tensor"])[feat]
-        K.fence(vis_raw, main_raw)              # (before the guide is enqueued: the towers may share one stream)
+        K.fence(vis_raw, main_raw)              # (before the guide is enqueued: the towers share one stream)
         if guide is not None:
             with K.launch_on(aux_raw):
                 gh = guide(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in)["decoder_hidden_states"][-1]   # TRAIN:293-294
-    else:
-        # id preprocessing + frozen guide forward on the aux stream, frozen ViT on its own stream: they depend only on
-        # the batch, so they fill the bubbles of the main chain (and of the previous step's AdamW)
-        for s_ in (aux, vis):
-            if ready is None:
-                s_.wait_stream(main)
-            else:
-                s_.wait_event(ready)
-        with torch.cuda.stream(aux):
-            src_mask, _ = K.prep_ids(src, cfg.pad_token_id)
-            tgt_mask, tgt_in = K.prep_ids(tgt, cfg.pad_token_id, start_id=cfg.eos_token_id)
-            ev_prep = torch.cuda.Event()
-            ev_prep.record(aux)
-            if guide is not None:
-                gh = guide(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in)["decoder_hidden_states"][-1]   # TRAIN:293-294
-        with torch.cuda.stream(vis):
-            img_cls = extract_clip_img_feat(net.clip_model, batch["img_tensor"])[feat]
-        main.wait_event(ev_prep)
-        main.wait_stream(vis)
-        for tns in (src_mask, tgt_mask, tgt_in, img_cls):
-            tns.record_stream(main)
-        for tns in (src, tgt):
-            tns.record_stream(aux)
-        batch["img_tensor"].record_stream(vis)
     kw = {}
     if not cfg.only_image:
         names_mask, _ = K.prep_ids(batch["names_art_ids"], cfg.pad_token_id)                 # TRAIN:270
@@ -239,12 +215,10 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
     if guide is not None:
         if towers is not None and _PLAN is not None:
             _PLAN.mark("join_guide")             # the host makes the compute stream wait for the guide graph here
-        elif aux is not None and towers is None and streams.explicit():
+        elif aux is not None and towers is None:
             K.fence(streams.raw("aux"), K._stream())
         elif aux is not None:
-            main.wait_stream(aux)
-            if towers is None:
-                gh.record_stream(main)
+            main.wait_stream(aux)                # (eager tower graphs)
         else:
             gh = guide(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in)["decoder_hidden_states"][-1]   # TRAIN:293-294
         colam = ops.ColamFn.apply(out["decoder_hidden_states"][-1], gh, tgt_mask, args.margin, args.alpha)        # TRAIN:296-307
@@ -414,7 +388,7 @@ class PlannedTrainStep:
     of the step, GraphedTrainStep, runs its branches less concurrently and is slower); the ~1250 Python -> ctypes -> autograd
     round trips per step are gone from the launch path.
 
-    What makes a step replayable: explicit scheduling (streams.explicit(): no stream synchronisation hidden inside torch), no
+    What makes a step replayable: explicit scheduling (streams: no stream synchronisation hidden inside torch), no
     host<->device sync and no ATen kernel inside the step, per-step scalars in device memory (LR, step and dropout counters:
     vacnic_lr_step), and every buffer at its recorded address — the recording runs inside a private allocator pool that is
     kept, inputs are copied into static tensors before each replay.  world_size > 1: on the reducer's native path the bucket
@@ -429,8 +403,6 @@ class PlannedTrainStep:
         global _PLAN
         from . import _lib
         from . import ddp as _ddp
-        if streams.enabled() and not streams.explicit():
-            raise RuntimeError("PlannedTrainStep needs explicit scheduling (VACNIC_EXPLICIT_STREAMS=0 is set)")
         self.towers = towers
         self.ev_bwd = None
         self.static = {k: v.clone() for k, v in example_batch.items()}
