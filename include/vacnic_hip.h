@@ -410,25 +410,25 @@ int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const in
 /*
  * Persistent single-token decoder step: every BartDecoderLayer of one position (MFULL:793-890 with
  * past_key_value, eval mode: self-attention over the KV cache, cross-attention over the encoder K/V projected once, FFN, the
- * three post-LayerNorms) in ONE launch — one workgroup per CU, grid barriers between the 8 phases of a layer, the next
- * projection's weights prefetched into registers behind each barrier.  R <= 8 rows (beams x batch), d_model <= 1024 with
- * 64-wide heads, ffn_dim <= 4096.  Same accumulation order and rounding points as the kernel-per-op chain vacnic_gemv_ln_bf16 /
- * vacnic_gemm_bf16 (skinny) / vacnic_attn_fwd (Tq = 1); results agree to the last bit up to fma-contraction choices of the compiler.
+ * three post-LayerNorms) in ONE launch of max(d / 4, ffn / 16) co-resident workgroups.  The 8 phases of a layer hand their
+ * results over through tagged 16-byte units in the `slots` buffer (no grid barriers); the next projection's weights are
+ * prefetched into LDS while a workgroup waits for its inputs.  R <= 8 rows (beams x batch), d_model <= 1024 with 64-wide heads,
+ * ffn_dim <= 4096, d and ffn multiples of 16, L <= 120, max(d / 4, ffn / 16) <= min(256, CUs) and R x heads <= that count.
+ * The projections run on the matrix cores: their fp32 sums associate differently from the kernel-per-op chain
+ * vacnic_gemv_ln_bf16 / vacnic_gemm_bf16 (skinny) / vacnic_attn_fwd (Tq = 1), so results agree with it to bf16 tolerance, not
+ * to the bit.
  *   layers   DEVICE array [L] of vacnic_decoder_layer: bf16 weights row-major [N][K] contiguous (w_kvq = k|v|q stacked, [3d][d]),
  *            fp32 biases and LayerNorm parameters; cross_kv bf16 [rows][S][2d] (k|v per source position) with cross_bs
  *            elements between rows (0: all rows share one source — the beams of one caption).
- *   cache    bf16 [L][R][Tmax + 1][2d]: k|v of position t are written at [l][r][t][0:2d], q is parked at [l][r][t + 1][0:d].
+ *   cache    bf16 [L][R][Tmax + 1][2d]: k|v of position t are written at [l][r][t][0:2d] (the extra position is where the
+ *            kernel-per-op chain parks q).
  *   h0       bf16 [R][d]: embedding LayerNorm output of the new token (vacnic_embed_ln_fwd).
- *   hbuf/obuf/ctx/qbuf ([R][d]) and fbuf ([R][F]): scratch.  Grid-barrier variant: on return the last layer's un-normalised
- *            block output is obuf and its residual is hbuf[L & 1]; final_layer_norm of the last layer is left to the consumer
- *            (vacnic_gemv_ln_bf16 with the LM head).  Slot variant: obuf holds the decoder's final hidden rows (final_layer_norm
- *            applied), ready for the LM-head GEMM; its projections run on the matrix cores (fp32 sums associate differently
- *            from the VALU kernels: parity to bf16 tolerance, not to the bit).
+ *   obuf     bf16 [R][d]: on return the decoder's final hidden rows (final_layer_norm of the last layer applied), ready for
+ *            the LM-head GEMM.
  *   sync     vacnic_decoder_step_sync_bytes() bytes, zeroed ONCE by the caller; word [sync_bytes / 4 - 64] is an error flag the
- *            kernel raises (and leaves) if a wait times out — check it when the results are read back.
- *   slots    vacnic_decoder_step_slots_bytes(L) bytes, zeroed ONCE by the caller: the phases hand their results over through
- *            tagged 16-byte units in this buffer (no grid barriers; needs max(d / 4, ffn / 16) <= 256 co-resident workgroups and
- *            d, ffn multiples of 16).  NULL selects the grid-barrier variant (kept as the A/B baseline).
+ *            kernel raises (and leaves) if a wait times out — check it when the results are read back, and zero sync and slots
+ *            again before the next launch if it is set.
+ *   slots    vacnic_decoder_step_slots_bytes(L) bytes, zeroed ONCE by the caller: the phases' exchange buffer.
  */
 typedef struct {
   const void *w_kvq, *w_so, *w_cq, *w_co, *w_fc1, *w_fc2;
@@ -440,15 +440,15 @@ typedef struct {
 typedef struct {
   const vacnic_decoder_layer* layers;
   void* cache; const void* h0;
-  void* hbuf[2]; void* obuf; void* ctx; void* qbuf; void* fbuf;
+  void* obuf;
   const uint8_t* enc_mask;        /* uint8 [R][S], 0 = masked source position; may be NULL */
   uint32_t* sync;
   void* slots;
   int64_t L, R, d, H, F, S, t, Tmax;
   float eps, scale;
-  uint64_t* trace; int64_t trace_wg;   /* profiling aid, normally NULL: 100 MHz time stamps of workgroup trace_wg, uint64 [8 L][8]
-                                          ([phase][0] phase start, [1] inputs staged, [3] results stored, [4] stores acknowledged,
-                                          [5] arrived at the barrier + next weights issued) */
+  uint64_t* trace; int64_t trace_wg;   /* profiling aid, normally NULL: 100 MHz time stamps of workgroup trace_wg, uint64 [8 L + 1][8]
+                                          ([phase][1] inputs gathered, [2] LayerNorm applied, [3] results packed; [8 L][4] / [6]
+                                          wall clock and [5] / [7] shader clock at the start / end of the launch) */
 } vacnic_decoder_step_args;
 int64_t vacnic_decoder_step_sync_bytes(void);
 int64_t vacnic_decoder_step_slots_bytes(int64_t L);

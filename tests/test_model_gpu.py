@@ -460,12 +460,11 @@ def test_beam_search_kv_cache_matches_oracle_and_reference_golden():
     assert torch.equal(a.cpu(), want), (a.tolist(), want.tolist())
 
 
-@pytest.mark.parametrize("variant", ["slots", "barrier", "per_op"])
+@pytest.mark.parametrize("variant", ["slots", "per_op"])
 def test_config5_batch1_beam5_maxlen50_matches_reference_golden(variant, monkeypatch):
     """BASELINE configs[4] on its own code path (TRAIN:513-520, DDPINF:758-842, run_full_train.sh:10-11): batch 1, beam 5,
-    length_penalty 2.0, max_length 50 — R = 5 rows, i.e. the persistent single-launch decoder-step kernel (tagged-slot exchange by
-    default, grid-barrier variant, and the kernel-per-op chain as the third leg) with on-device beam bookkeeping, eagerly and as
-    hipGraph capture + replay.  Ids must equal tests/golden/generate_cfg5.npz — transformers' beam search over the REAL
+    length_penalty 2.0, max_length 50 — R = 5 rows, i.e. the persistent single-launch decoder-step kernel (tagged-slot exchange,
+    and the kernel-per-op chain as the second leg) with on-device beam bookkeeping, eagerly and as hipGraph capture + replay.  Ids must equal tests/golden/generate_cfg5.npz — transformers' beam search over the REAL
     reference model — and the oracle's restatement, with the library defaults, with the hub checkpoints' generation defaults
     (no-repeat 3-grams, early stopping, forced BOS), and with min_length 49 (all 50 positions decoded: the cache ping-pong, the
     per-layer beam gather and the early-exit poll every 8th position all run to the end).  Weights: oracle/cfg5_fixture.py
@@ -491,7 +490,6 @@ def test_config5_batch1_beam5_maxlen50_matches_reference_golden(variant, monkeyp
     dev = {k: v.cuda() for k, v in batch.items()}
     mask, _ = K.prep_ids(dev["article_ids"], 1)
     nmask, _ = K.prep_ids(dev["names_art_ids"], 1)
-    monkeypatch.setenv("VACNIC_DECODE_BARRIER", "1" if variant == "barrier" else "0")
     monkeypatch.setenv("VACNIC_DECODE_PER_OP", "1" if variant == "per_op" else "0")
 
     def run(extra, **kw):
@@ -513,7 +511,7 @@ def test_config5_batch1_beam5_maxlen50_matches_reference_golden(variant, monkeyp
         for s_ in ses:                                                   # the code path config 5 runs on
             assert s_.dec.step_kernel == (variant != "per_op"), (variant, "decoder-step kernel selection")
             if variant != "per_op":
-                assert (s_.dec.slots is not None) == (variant == "slots"), (variant, "exchange variant")
+                assert s_.dec.slots is not None, (variant, "tagged-slot exchange")
         for rep in range(2):                                             # 2nd call captures every position as a hipGraph, 3rd replays
             again = run(extra)
             assert torch.equal(again.cpu(), want), (variant, name, "graph", rep, again.tolist(), want.tolist())
@@ -591,7 +589,7 @@ def test_config5_sensitive_fixture_all_beams_and_mutations(monkeypatch):
     dev = {k: v.cuda() for k, v in batch.items()}
     mask, _ = K.prep_ids(dev["article_ids"], 1)
     nmask, _ = K.prep_ids(dev["names_art_ids"], 1)
-    monkeypatch.setenv("VACNIC_DECODE_BARRIER", "0"); monkeypatch.setenv("VACNIC_DECODE_PER_OP", "0")
+    monkeypatch.setenv("VACNIC_DECODE_PER_OP", "0")
     LP, ML = F5.LENGTH_PENALTY, F5.MAX_LENGTH
 
     def run(extra, **kw):
@@ -1194,16 +1192,14 @@ def test_planned_step_draws_fresh_dropout_masks_every_replay():
         streams.enable(False)
 
 
-@pytest.mark.parametrize("variant", ["slots", "barrier"])
 @pytest.mark.parametrize("case", ["bart_base_shape", "bart_large_shape"])
-def test_decoder_step_kernel_matches_per_op_path(case, variant, monkeypatch):
-    """the persistent decoder-step kernel (all layers of a position in ONE launch, grid barriers between the
-    phases) against the kernel-per-op chain it replaces (gemv_ln / skinny GEMM / single-query attention), including beam reorders
-    between positions, a masked source and both attention key-split modes (S < 256: one wave per (row, head); S >= 256: four).
-    Same accumulation order, reduction trees and bf16 rounding points: KV-cache rows and logits agree bit for bit except where
-    the two compilations contract an fma differently (one bf16 ulp on a rare activation, which then moves every logit of that
-    row in the last bits) — gate: every logit within 2e-2 and identical arg-max ids at every position, >= 90 % of the
-    (position, row) pairs bit-equal over the run, and the step kernel reproduces itself exactly."""
+def test_decoder_step_kernel_matches_per_op_path(case, monkeypatch):
+    """the persistent decoder-step kernel (all layers of a position in ONE launch, the phases exchanging through
+    tagged slots) against the kernel-per-op chain it replaces (gemv_ln / skinny GEMM / single-query attention), including beam
+    reorders between positions, a masked source and both attention key-split modes (S < 256: one wave per (row, head); S >= 256:
+    four).  The step kernel's projections run on the matrix cores, whose fp32 sums associate differently, so activations differ
+    by a bf16 ulp here and there — gate: KV-cache rows and logits within tolerance, arg-max ids equal up to near ties at every
+    position, and the step kernel reproduces itself exactly."""
     from vacnic_amd import generate as Gn, synthetic
     from vacnic_amd.config import ClipVisionConfig
     from vacnic_amd.training import build_models
@@ -1226,15 +1222,12 @@ def test_decoder_step_kernel_matches_per_op_path(case, variant, monkeypatch):
     mask = torch.ones(B, S, dtype=torch.uint8)
     mask[:, S - 5:] = 0                                        # padded source tail
     mask = mask.cuda()
-    # the two exchange mechanisms of the step kernel: tagged slots (default, no grid barriers) and grid barriers
-    monkeypatch.setenv("VACNIC_DECODE_BARRIER", "1" if variant == "barrier" else "0")
     fast = Gn.CachedDecoder(model, R, S, Tmax, reorders=True)
     assert fast.step_kernel, "the step kernel must be the default for <= 8 rows"
-    assert (fast.slots is not None) == (variant == "slots")
+    assert fast.slots is not None
     monkeypatch.setenv("VACNIC_DECODE_PER_OP", "1")
     ref = Gn.CachedDecoder(model, R, S, Tmax, reorders=True)
     assert not ref.step_kernel
-    exact = 0
     with torch.no_grad():
         fast.begin(enc_h, mask, nb); ref.begin(enc_h, mask, nb)
         for t in range(Tmax - 1):
@@ -1247,21 +1240,12 @@ def test_decoder_step_kernel_matches_per_op_path(case, variant, monkeypatch):
             lb = ref.step(ids, t)[:, :model.V]
             torch.cuda.synchronize()
             ca, cb = fast.cache_at(t)[:, :, :t + 1, :2 * cfg.d_model].float(), ref.cache_at(t)[:, :, :t + 1, :2 * cfg.d_model].float()
-            if variant == "barrier":
-                # same VALU arithmetic as the per-op kernels: equal to the bit except for rare fma-contraction differences
-                assert (ca == cb).float().mean().item() >= 0.999 and (ca - cb).abs().max().item() <= 2e-2, (case, t, "KV cache rows differ")
-                assert (la - lb).abs().max().item() <= 2e-2, (case, t, (la - lb).abs().max().item())
-                assert torch.equal(la.argmax(-1), lb.argmax(-1)), (case, t)
-                exact += int((la == lb).all(dim=1).sum().item())
-            else:
-                # projections on the matrix cores: fp32 sums associate differently -> bf16 activations differ by an ulp here and there
-                assert ((ca - cb).norm() / cb.norm()).item() <= 5e-3 and (ca - cb).abs().max().item() <= 6e-2, (case, t, (ca - cb).abs().max().item())
-                assert (la - lb).abs().max().item() <= 0.15 and ((la - lb).norm() / lb.norm()).item() <= 1e-2, (case, t, (la - lb).abs().max().item())
-                pick = lb.gather(1, la.argmax(-1, keepdim=True))
-                assert bool((pick >= lb.max(-1, keepdim=True).values - 0.15).all()), (case, t, "arg-max differs beyond a near tie")
-                exact = R * (Tmax - 1)
+            # projections on the matrix cores: fp32 sums associate differently -> bf16 activations differ by an ulp here and there
+            assert ((ca - cb).norm() / cb.norm()).item() <= 5e-3 and (ca - cb).abs().max().item() <= 6e-2, (case, t, (ca - cb).abs().max().item())
+            assert (la - lb).abs().max().item() <= 0.15 and ((la - lb).norm() / lb.norm()).item() <= 1e-2, (case, t, (la - lb).abs().max().item())
+            pick = lb.gather(1, la.argmax(-1, keepdim=True))
+            assert bool((pick >= lb.max(-1, keepdim=True).values - 0.15).all()), (case, t, "arg-max differs beyond a near tie")
             if t == Tmax - 2:                                   # determinism: the same position again gives the same bits
                 again = fast.step(ids, t)[:, :model.V]
                 assert torch.equal(again, la), (case, "step kernel is not deterministic")
-    assert exact >= 0.9 * R * (Tmax - 1), (case, exact, "nearly all (position, row) pairs should match the per-op chain exactly")
     fast.check_step_kernel()

@@ -15,6 +15,7 @@ g = torch.Generator().manual_seed(0)
 enc_h = (torch.randn(1, S, cfg.d_model, generator=g) * 0.5).bfloat16().cuda()
 mask = torch.ones(1, S, dtype=torch.uint8).cuda()
 dec = Gn.CachedDecoder(model, R, S, Tmax, reorders=True)
+assert dec.step_kernel, "this shape does not run on the decoder-step kernel"
 L = dec.L
 names = ["P1 LN+kvq", "P2 self-attn", "P3 out", "P4 LN+q", "P5 cross-attn", "P6 out", "P7 LN+fc1", "P8 fc2"]
 with torch.no_grad():
@@ -28,33 +29,20 @@ with torch.no_grad():
         dec.step(ids, 30)
         torch.cuda.synchronize()
         tr = dec.trace.cpu().view(-1, 8).double() / 100.0          # us
-        if dec.slots is not None:
-            raw = dec.trace.cpu().view(-1, 8)
-            dw, dc = (raw[8 * L, 6] - raw[8 * L, 4]).item(), (raw[8 * L, 7] - raw[8 * L, 5]).item()
-            print(f"shader clock during the kernel: {dc} cycles in {dw / 100.0:.1f} us = {dc / (dw / 100.0) / 1e3:.2f} GHz")
-            print(f"workgroup {wg} (slot variant): kernel span {(tr[8 * L - 1, 3] - tr[0, 1]).item():.1f} us over {8 * L} phases")
-            print("  phase            wait+gather   compute+pack    total   (attention phases: pair workgroups only)")
-            for k in range(8):
-                rows = [ph for ph in range(8, 8 * L) if ph % 8 == k and tr[ph, 3] > 0 and tr[ph, 1] > 0]
-                if not rows:
-                    continue
-                prev = lambda ph: max(tr[q, 3].item() for q in range(max(0, ph - 3), ph))
-                ga = sum(tr[ph, 1].item() - prev(ph) for ph in rows) / len(rows)
-                co = sum((tr[ph, 3] - tr[ph, 1]).item() for ph in rows) / len(rows)
-                ln = [ph for ph in rows if tr[ph, 2] > 0]
-                lns = f"   (LayerNorm {sum((tr[ph, 2] - tr[ph, 1]).item() for ph in ln) / len(ln):.2f})" if ln else ""
-                print(f"  {names[k]:14s} {ga:11.2f} {co:14.2f} {ga + co:8.2f}{lns}")
-            continue
+        raw = dec.trace.cpu().view(-1, 8)
+        dw, dc = (raw[8 * L, 6] - raw[8 * L, 4]).item(), (raw[8 * L, 7] - raw[8 * L, 5]).item()
+        print(f"shader clock during the kernel: {dc} cycles in {dw / 100.0:.1f} us = {dc / (dw / 100.0) / 1e3:.2f} GHz")
         print(f"workgroup {wg}: kernel span {(tr[8 * L - 1, 3] - tr[0, 1]).item():.1f} us over {8 * L} phases")
-        print("  phase            stage   compute+store  store-ack  arrive+issue  barrier-wait   total")
+        print("  phase            wait+gather   compute+pack    total   (attention phases: pair workgroups only)")
         for k in range(8):
-            rows = [ph for ph in range(8, 8 * L - 1) if ph % 8 == k]
-            st = sum((tr[ph, 1] - tr[ph, 0]).item() for ph in rows) / len(rows) if k not in (1, 4) else float("nan")
-            cs = sum((tr[ph, 3] - (tr[ph, 1] if k not in (1, 4) else tr[ph, 0])).item() for ph in rows) / len(rows)
-            ack = sum((tr[ph, 4] - tr[ph, 3]).item() for ph in rows) / len(rows)
-            arr = sum((tr[ph, 5] - tr[ph, 4]).item() for ph in rows) / len(rows)
-            bw = sum((tr[ph + 1, 0] - tr[ph, 5]).item() for ph in rows) / len(rows)
-            tot = sum((tr[ph + 1, 0] - tr[ph, 0]).item() for ph in rows) / len(rows)
-            print(f"  {names[k]:14s} {st:7.2f} {cs:12.2f} {ack:11.2f} {arr:12.2f} {bw:12.2f} {tot:9.2f}")
+            rows = [ph for ph in range(8, 8 * L) if ph % 8 == k and tr[ph, 3] > 0 and tr[ph, 1] > 0]
+            if not rows:
+                continue
+            prev = lambda ph: max(tr[q, 3].item() for q in range(max(0, ph - 3), ph))
+            ga = sum(tr[ph, 1].item() - prev(ph) for ph in rows) / len(rows)
+            co = sum((tr[ph, 3] - tr[ph, 1]).item() for ph in rows) / len(rows)
+            ln = [ph for ph in rows if tr[ph, 2] > 0]
+            lns = f"   (LayerNorm {sum((tr[ph, 2] - tr[ph, 1]).item() for ph in ln) / len(ln):.2f})" if ln else ""
+            print(f"  {names[k]:14s} {ga:11.2f} {co:14.2f} {ga + co:8.2f}{lns}")
     dec.trace = None
     dec.check_step_kernel()

@@ -133,8 +133,7 @@ DecoderLayer = _struct("vacnic_decoder_layer", [
     ("cross_kv", vp), ("cross_bs", i64)])
 
 DecoderStepArgs = _struct("vacnic_decoder_step_args", [
-    ("layers", vp), ("cache", vp), ("h0", vp), ("hbuf0", vp), ("hbuf1", vp), ("obuf", vp), ("ctx", vp), ("qbuf", vp), ("fbuf", vp),
-    ("enc_mask", vp), ("sync", vp), ("slots", vp),
+    ("layers", vp), ("cache", vp), ("h0", vp), ("obuf", vp), ("enc_mask", vp), ("sync", vp), ("slots", vp),
     ("L", i64), ("R", i64), ("d", i64), ("H", i64), ("F", i64), ("S", i64), ("t", i64), ("Tmax", i64), ("eps", f32), ("scale", f32),
     ("trace", vp), ("trace_wg", i64)])
 

@@ -4,145 +4,81 @@
 // over the encoder K/V projected once, FFN, three post-LayerNorms; eval mode) for all decoder layers of one position — 8 dependent
 // launches per layer in the kernel-per-op path (gemv_ln / gemm_skinny / attn_decode), each 6-12 us for 2-8 MB of weights.
 //
-// Design.  G = one workgroup per CU (256 threads) walks the 8 phases of every layer; phases are separated by a grid barrier
-// (two-level arrive over 16 counters + 16 release flags on their own cache lines: 1.6 us at G = 256, tools/gridbar_probe.hip)
-// instead of a kernel boundary (~5 us + cold caches), and the weights of the NEXT projection are pulled into registers between
-// the arrive and the wait of a barrier — they do not depend on the activations, so the HBM round trip of a phase is hidden
-// behind the barrier it follows.
-//   P1  x = LN(o + h)      -> k|v|q = x Wkvq^T + b        (written in place into the KV cache row of position t)
-//   P2  self-attention over cache[0..t]                     one (row, head) pair per workgroup
+// Design.  G = max(d / 4, F / 16) co-resident workgroups (256 threads) walk the 8 phases of every layer with no grid barrier: a
+// phase's producers hand their results to the consumers through TAGGED SLOTS in HBM.  A slot is a run of 16-byte units {6 bf16
+// values, 32-bit tag}, written with one coherent (sc1) 16-byte store per unit and NO wait for the acknowledgement; a consumer
+// thread polls "its" producer's slot until every unit carries the tag of (this launch, this phase) and scatters the values into
+// the workgroup's LDS copy of the activation.  The data IS the signal, so a phase boundary costs one store-to-visible latency
+// plus one poll round trip (~1.5 us; tools/gridbar_probe.hip measures the coherent exchange) instead of a kernel boundary (~5 us
+// + cold caches).  Tag = nonce * 1024 + phase, nonce = a per-buffer launch counter (read by everybody at the start, bumped by
+// workgroup 0 at its exit — which cannot happen before every workgroup has produced its last phase), so a stale slot can never
+// match.  A slot array is reused once per layer: whoever produces phase X of layer l+1 has consumed data that transitively
+// required every workgroup to be past its read of (l, X).  The residual stream h never leaves the chip: every workgroup
+// normalises all rows anyway and keeps h in LDS.  The next projection's weights are pulled into LDS by DMA while the workgroup
+// waits for its inputs — they do not depend on the activations.
+//   P1  x = LN(o + h)      -> k|v|q = x Wkvq^T + b        (k|v also stored to the cache row of position t)
+//   P2  self-attention over cache[0..t-1] and the new row   one (row, head) pair per workgroup
 //   P3  o = ctx Wo^T + b
 //   P4  x = LN(o + h) -> h -> q = x Wq^T + b
 //   P5  cross-attention over the encoder K/V (key mask)     one (row, head) pair per workgroup, 4 waves split the keys
 //   P6  o = ctx Wo^T + b
 //   P7  x = LN(o + h) -> h -> f = gelu(x W1^T + b)
-//   P8  o = f W2^T + b                                      (the last layer's (o, h) pair is normalised by the LM-head kernel)
-// Activations that cross a phase (k|v|q, ctx, o, h, q, f: <= 8 rows) live in HBM and are exchanged with sc1 buffer loads /
-// stores (agent-coherent: write-through, miss-always in the XCD's L2; a store is complete when vmcnt says so) — release /
-// acquire fences (buffer_wbl2 / buffer_inv) cost 20-35 us per phase on this part, sc1 traffic costs nothing measurable.
-// Weights, the cross-attention K/V and LayerNorm parameters are read-only for the launch and use ordinary cached loads.
+//   P8  o = f W2^T + b                                      (workgroup 0 applies the last layer's final LayerNorm -> obuf)
 //
-// Arithmetic: the same per-lane accumulation order, wave-reduction tree and bf16 rounding points as vacnic_gemv_ln_bf16,
-// gemm_skinny_kernel and attn_decode_kernel: the logits of a position match the kernel-per-op path bit for bit except where the
-// two compilations contract an fma differently (one bf16 ulp on a rare activation; -ffp-contract=fast leaves that to the
-// optimiser) — tests/test_model_gpu.py::test_decoder_step_kernel_matches_per_op_path.
+// Arithmetic: LayerNorm and attention keep the per-lane order and bf16 rounding points of add_ln_fwd_kernel and
+// attn_decode_kernel, but the projections run on the matrix cores (v_mfma_f32_16x16x32_bf16) and their fp32 sums associate
+// differently from the VALU kernels of the per-op chain: activations differ by a bf16 ulp here and there, so parity with the
+// per-op chain holds to a tolerance, not to the bit — tests/test_model_gpu.py::test_decoder_step_kernel_matches_per_op_path.
 //
-// Safety: a barrier wait that exceeds ~2 s (100 MHz wall clock) sets the error word and every workgroup leaves; the last
-// workgroup out clears the barrier state, so a launch always drains and the next one starts clean.
+// Safety: a poll that exceeds ~2 s (100 MHz wall clock) sets the error word of the sync buffer and every workgroup leaves; the
+// nonce is then not bumped and the caller must clear the sync and slot buffers before the next launch.
 #include "common.h"
 
 namespace {
 
 constexpr int NTHR = 256, NWAVE = 4, MR = 8;
-constexpr int NGRP = 16, NFLAG = 16;
 constexpr int COH = 16;                       // aux bits of the buffer intrinsics: sc1
-// barrier state (uint32 words, one 128-byte line each): grp[16] | top | flag[16] | exit | err
-constexpr int BAR_TOP = 32 * NGRP, BAR_FLAG = 32 * (NGRP + 1), BAR_EXIT = 32 * (NGRP + 1 + NFLAG), BAR_ERR = BAR_EXIT + 32;
+// sync buffer (uint32 words, one 128-byte line each): the error word and the launch nonce.  They stay at the word offsets of the
+// retired grid-barrier layout, and DecP keeps that variant's five scratch pointers as padding: the kernel runs at the register
+// limit (104 SGPRs, ~780 of them spilled to VGPR lanes), and moving an argument or a constant offset re-rolls its whole register
+// allocation.  With both kept, its code is what it was when the barrier variant shipped beside it.
+constexpr int BAR_ERR = 34 * 32, BAR_NONCE = BAR_ERR + 32;
 #define AGENT __HIP_MEMORY_SCOPE_AGENT
 
 struct DecP {
   const vacnic_decoder_layer* layers;
   bf16_t* cache; const bf16_t* h0;
-  bf16_t *hb0, *hb1, *o, *ctx, *q, *f;
+  void* pad0_[2];                             // unused (see BAR_ERR)
+  bf16_t* o;
+  void* pad1_[3];
   const uint8_t* enc_mask;
   unsigned* bar;
   int L, R, d, H, F, S, t, Tstride;           // Tstride = (Tmax + 1) * 2d elements between two rows of one layer's cache
   unsigned cache_bytes, xs_bytes;
   float eps, scale;
   unsigned long long* trace; int trace_wg;    // profiling aid: 100 MHz time stamps of one workgroup, [phase][8]
-  char* slots;                                // tagged-slot exchange buffers (slot variant)
+  char* slots;                                // tagged-slot exchange buffers
 };
 
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 __device__ __forceinline__ rsrc_t mkrs(const void* p, unsigned bytes) { return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, bytes, 0x00020000); }
 __device__ __forceinline__ u32x4 cld(rsrc_t rs, unsigned off) { return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, COH); }
 __device__ __forceinline__ void cst(u32x4 v, rsrc_t rs, unsigned off) { __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, COH); }
-__device__ __forceinline__ void cst16(float v, rsrc_t rs, unsigned off) { __builtin_amdgcn_raw_buffer_store_b16((short)f2bf(v), rs, off, 0, COH); }
 
 __device__ __forceinline__ void unpack8(u32x4 r, float v[8]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
 }
 
-// ---- grid barrier ------------------------------------------------------------------------------------------------
-struct Bar { unsigned* base; int G; unsigned ph; bool last; };
-
-// every thread has waited for its own stores (s_waitcnt vmcnt(0)) before this
-__device__ __forceinline__ void bar_arrive(Bar& b) {
-  __syncthreads();
-  b.ph += 1;
-  if (threadIdx.x == 0) {
-    const int g = blockIdx.x % NGRP;
-    const unsigned gsize = (unsigned)((b.G - g + NGRP - 1) / NGRP);
-    const unsigned ngrp = (unsigned)(b.G < NGRP ? b.G : NGRP);
-    bool last = __hip_atomic_fetch_add(b.base + 32 * g, 1u, __ATOMIC_RELAXED, AGENT) + 1 == b.ph * gsize;
-    if (last) last = __hip_atomic_fetch_add(b.base + BAR_TOP, 1u, __ATOMIC_RELAXED, AGENT) + 1 == b.ph * ngrp;
-    if (last) {
-#pragma unroll
-      for (int f = 0; f < NFLAG; ++f) __hip_atomic_store(b.base + BAR_FLAG + 32 * f, b.ph, __ATOMIC_RELAXED, AGENT);
-    }
-    b.last = last;
-  }
-}
-__device__ __forceinline__ bool bar_wait(Bar& b, int* s_bad) {
-  if (threadIdx.x == 0) {
-    if (!b.last) {
-      unsigned* fl = b.base + BAR_FLAG + 32 * (blockIdx.x % NFLAG);
-      const long long t0 = wall_clock64();
-      unsigned polls = 0;
-      while (__hip_atomic_load(fl, __ATOMIC_RELAXED, AGENT) < b.ph) {
-        __builtin_amdgcn_s_sleep(1);
-        if ((++polls & 1023u) == 0 &&
-            (wall_clock64() - t0 > 200000000ll || __hip_atomic_load(b.base + BAR_ERR, __ATOMIC_RELAXED, AGENT) != 0)) {
-          __hip_atomic_store(b.base + BAR_ERR, 1u, __ATOMIC_RELAXED, AGENT);
-          *s_bad = 1;
-          break;
-        }
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's prefetch DMA has landed -> visible to the whole workgroup below
-  __syncthreads();
-  return *s_bad == 0;
-}
-
 // ---- weight prefetch --------------------------------------------------------------------------------------------------
-// The next projection's weights are ISSUED between the arrive and the wait of a barrier and must stay in flight across it.
-// They go HBM -> LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`: no destination VGPRs, so nothing the register allocator could
-// move or spill while the data is still on its way, and an intrinsic with side effects is not sunk behind the wait the way
-// plain C++ loads were).  Every wave owns private 1-KiB slots (one per 64-lane x 16-byte piece: lane-linear, conflict-free
-// to read back) and only ever reads its own, so `s_waitcnt vmcnt(0)` by that wave is all the synchronisation needed.
-// Columns >= N and chunks >= K / 8 point outside the descriptor and are zero-filled.
+// The next projection's weights are ISSUED as soon as the workgroup has finished with the previous ones and stay in flight
+// while it waits for its inputs.  They go HBM -> LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`: no destination VGPRs, so nothing
+// the register allocator could move or spill while the data is still on its way).  Every wave owns private 1-KiB slots
+// (lane-linear, conflict-free to read back).  Columns >= N and chunks >= K / 8 point outside the descriptor and are zero-filled.
 constexpr unsigned OOB = 0x7ffffff0u;
-constexpr int WBIG = 8 * 1024, WSMALL = 2 * 1024;       // bytes per wave: 4 columns x 2 chunks / 1 column x 2 chunks
+constexpr int WBIG = 8 * 1024, WSMALL = 2 * 1024;       // bytes per wave: k|v|q, fc1, fc2 tiles / d-wide projection tiles
 __device__ __forceinline__ void wdma(rsrc_t wrs, char* slot, unsigned voff) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, LDS_PTR(slot), 16, (int)voff, 0, 0, 0);
-}
-__device__ __forceinline__ void w_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ u32x4 w_get(const char* wl, int slot, int lane) { return *(const u32x4*)(wl + slot * 1024 + lane * 16); }
-
-// C columns n0 .. n0+C-1 of W [N][K] for one wave, K <= 1024: chunks lane, lane + 64 -> slots c * 2 + i
-template <int C>
-__device__ __forceinline__ void w_issue(char* wl, rsrc_t wrs, int N, int K, int n0, int lane) {
-  const int nchunk = K >> 3;
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ch = lane + 64 * i, n = n0 + c;
-      wdma(wrs, wl + (c * 2 + i) * 1024, (ch < nchunk && n < N) ? (unsigned)(n * K + ch * 8) * 2u : OOB);
-    }
-}
-// 4 columns per workgroup, K <= 4096 split over the 4 waves: chunks lane + 64 * wave + 256 * i
-__device__ __forceinline__ void w2_issue(char* wl, rsrc_t wrs, int N, int K, int n0, int wave, int lane) {
-  const int nchunk = K >> 3;
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ch = lane + 64 * wave + 256 * i, n = n0 + c;
-      wdma(wrs, wl + (c * 2 + i) * 1024, (ch < nchunk && n < N) ? (unsigned)(n * K + ch * 8) * 2u : OOB);
-    }
 }
 
 // LayerNorm parameters (fp32 gamma | beta, K <= 1024 each) into the workgroup's shared slot: wave w moves piece w of both
@@ -158,241 +94,6 @@ __device__ __forceinline__ void bias_issue(float* biasl, const float* bias, int 
   if (wave == 0) {
     const rsrc_t rb = mkrs(bias, bias ? (unsigned)N * 4u : 0u);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, LDS_PTR(biasl), 4, (int)((lane < ncols && n_first + lane < N) ? (unsigned)(n_first + lane) * 4u : OOB), 0, 0, 0);
-  }
-}
-
-struct OutD { rsrc_t rs; unsigned base, rstride; };     // byte offset of (row 0, column 0) and row stride in bytes
-
-// reduce-scatter butterflies over the 64 lanes (xor offsets 32, 16, 8, 4, 2, 1 — the tree of gemm_skinny_kernel)
-#define VAC_BFLY(OFF, HALF)                                                      \
-  {                                                                              \
-    const bool up = (lane & OFF) != 0;                                           \
-    _Pragma("unroll") for (int i = 0; i < HALF; ++i) {                           \
-      const float send = up ? acc[i] : acc[HALF + i];                            \
-      const float keep = up ? acc[HALF + i] : acc[i];                            \
-      acc[i] = keep + __shfl_xor(send, OFF, 64);                                 \
-    }                                                                            \
-  }
-__device__ __forceinline__ float bfly32(float (&acc)[32], int lane, int& idx, bool& owner) {
-  VAC_BFLY(32, 16) VAC_BFLY(16, 8) VAC_BFLY(8, 4) VAC_BFLY(4, 2) VAC_BFLY(2, 1)
-  const float v = acc[0] + __shfl_xor(acc[0], 1, 64);
-  idx = (((lane >> 5) & 1) << 4) | (((lane >> 4) & 1) << 3) | (((lane >> 3) & 1) << 2) | (((lane >> 2) & 1) << 1) | ((lane >> 1) & 1);
-  owner = (lane & 1) == 0;
-  return v;
-}
-__device__ __forceinline__ float bfly8(float (&acc)[8], int lane, int& idx, bool& owner) {
-  VAC_BFLY(32, 4) VAC_BFLY(16, 2) VAC_BFLY(8, 1)
-  float v = acc[0];
-  v += __shfl_xor(v, 4, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 1, 64);
-  idx = (((lane >> 5) & 1) << 2) | (((lane >> 4) & 1) << 1) | ((lane >> 3) & 1);
-  owner = (lane & 7) == 0;
-  return v;
-}
-#undef VAC_BFLY
-
-// one wave: the dot products of C weight rows (this wave's prefetch slots) with all R rows of x (bf16, LDS, [R][K]); after the
-// reduce-scatter butterfly `owner` lanes hold the sum of (row idx / C, column idx % C)
-template <int C>
-__device__ __forceinline__ float gemv_reduce(const char* wl, const bf16_t* xs, int R, int K, int lane, int& idx, bool& owner) {
-  constexpr int NV = MR * C;
-  float acc[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) acc[i] = 0.f;
-  const int nchunk = K >> 3;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ch = lane + 64 * i;
-    if (ch < nchunk) {
-      float wv[C][8];
-#pragma unroll
-      for (int c = 0; c < C; ++c) unpack8(w_get(wl, c * 2 + i, lane), wv[c]);
-#pragma unroll
-      for (int m = 0; m < MR; ++m) {
-        if (m < R) {
-          float xv[8];
-          unpack8(*(const u32x4*)(xs + (size_t)m * K + ch * 8), xv);
-#pragma unroll
-          for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[m * C + c] += xv[j] * wv[c][j];
-        }
-      }
-    }
-  }
-  if constexpr (C == 4) return bfly32(acc, lane, idx, owner);
-  else return bfly8(acc, lane, idx, owner);
-}
-
-// one wave: C output columns n0 .. n0+C-1 for all R rows
-template <int C>
-__device__ __forceinline__ void gemv_tile(const char* wl, const bf16_t* xs, int R, int N, int K, int n0, const float* bias, const float* biasl,
-                                          int act, const OutD& o, int lane) {
-  int idx; bool owner;
-  float v = gemv_reduce<C>(wl, xs, R, K, lane, idx, owner);
-  if (owner) {
-    const int m = idx / C, c = idx % C, n = n0 + c;
-    if (m < R && n < N) {
-      if (biasl) v += biasl[c];
-      else if (bias) v += bias[n];
-      v = act_fwd(act, v);
-      cst16(v, o.rs, o.base + (unsigned)m * o.rstride + (unsigned)n * 2u);
-    }
-  }
-}
-
-template <int C>
-__device__ __forceinline__ void gemv_phase(char* wl, rsrc_t wrs, const float* bias, const float* biasl, int N, int K, int act, const OutD& o,
-                                           const bf16_t* xs, int R, int G, int wg, int wave, int lane) {
-  const int ntile = (N + NWAVE * C - 1) / (NWAVE * C);
-  for (int T = wg; T < ntile; T += G) {
-    const int n0 = (T * NWAVE + wave) * C;
-    if (T != wg) { w_issue<C>(wl, wrs, N, K, n0, lane); w_wait(); }         // tiles beyond the prefetched one (N > 4 C G)
-    gemv_tile<C>(wl, xs, R, N, K, n0, bias, T == wg ? biasl + wave * C : nullptr, act, o, lane);
-  }
-}
-
-// long reduction (fc2): a workgroup owns 4 columns, its 4 waves split K and meet in LDS (gemm_skinny_kernel<8, 4, 4>)
-__device__ __forceinline__ void gemv2_phase(char* wl, rsrc_t wrs, const float* bias, const float* biasl, int N, int K, const OutD& o, const bf16_t* xs,
-                                            int R, int G, int wg, int wave, int lane, float (*part)[32]) {
-  const int ntile = (N + 3) / 4;
-  const int nchunk = K >> 3;
-  for (int T = wg; T < ntile; T += G) {
-    const int n0 = T * 4;
-    if (T != wg) { w2_issue(wl, wrs, N, K, n0, wave, lane); w_wait(); }
-    float acc[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc[i] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ch = lane + 64 * wave + 256 * i;
-      if (ch < nchunk) {
-        float wv[4][8];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) unpack8(w_get(wl, c * 2 + i, lane), wv[c]);
-#pragma unroll
-        for (int m = 0; m < MR; ++m) {
-          if (m < R) {
-            float xv[8];
-            unpack8(*(const u32x4*)(xs + (size_t)m * K + ch * 8), xv);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-              for (int j = 0; j < 8; ++j) acc[m * 4 + c] += xv[j] * wv[c][j];
-          }
-        }
-      }
-    }
-    int idx; bool owner;
-    float v = bfly32(acc, lane, idx, owner);
-    if (owner) part[wave][idx] = v;
-    __syncthreads();
-    if (wave == 0 && owner) {
-      v = 0.f;
-#pragma unroll
-      for (int w = 0; w < NWAVE; ++w) v += part[w][idx];
-      const int m = idx / 4, c = idx % 4, n = n0 + c;
-      if (m < R && n < N) {
-        if (T == wg) v += biasl[c];
-        else if (bias) v += bias[n];
-        cst16(v, o.rs, o.base + (unsigned)m * o.rstride + (unsigned)n * 2u);
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---- x -> LDS ------------------------------------------------------------------------------------------------------
-// rows of a phase-crossing activation (bf16 [R][K], contiguous) into LDS
-__device__ __forceinline__ void stage_plain(rsrc_t src, bf16_t* xs, int R, int K, int tid) {
-  const int n = R * (K >> 3);
-  for (int c0 = tid; c0 < n; c0 += 4 * NTHR) {
-    u32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + u * NTHR;
-      v[u] = c < n ? cld(src, (unsigned)c * 16u) : (u32x4){0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int c = c0 + u * NTHR;
-      if (c < n) *(u32x4*)(xs + (size_t)c * 8) = v[u];
-    }
-  }
-}
-
-// x = LayerNorm(o + h) (add_ln_fwd_kernel's arithmetic: one wave per row, chunks lane / lane + 64, fp32 statistics), rounded
-// to bf16 into LDS; workgroup 0 also writes the rows to hnew — the next block's residual.
-__device__ __forceinline__ void stage_ln(rsrc_t osrc, rsrc_t hsrc, const float* lnp, rsrc_t hnew, bool write_h,
-                                         bf16_t* xs, int R, int K, float eps, int wave, int lane) {
-  const int nchunk = K >> 3;
-  u32x4 xraw[2][2], rraw[2][2];
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr)
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int m = wave + NWAVE * rr, ch = lane + 64 * i;
-      xraw[rr][i] = (u32x4){0, 0, 0, 0}; rraw[rr][i] = (u32x4){0, 0, 0, 0};
-      if (m < R && ch < nchunk) {
-        xraw[rr][i] = cld(osrc, (unsigned)(m * K + ch * 8) * 2u);
-        rraw[rr][i] = cld(hsrc, (unsigned)(m * K + ch * 8) * 2u);
-      }
-    }
-  float gam[2][8], bet[2][8];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int ch = lane + 64 * i;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { gam[i][j] = 0.f; bet[i][j] = 0.f; }
-    if (ch < nchunk) {
-      const f32x4 g0 = *(const f32x4*)(lnp + ch * 8), g1 = *(const f32x4*)(lnp + ch * 8 + 4);
-      const f32x4 b0 = *(const f32x4*)(lnp + 1024 + ch * 8), b1 = *(const f32x4*)(lnp + 1024 + ch * 8 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { gam[i][j] = g0[j]; gam[i][4 + j] = g1[j]; bet[i][j] = b0[j]; bet[i][4 + j] = b1[j]; }
-    }
-  }
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr) {
-    const int m = wave + NWAVE * rr;
-    if (m >= R) continue;
-    float h[2][8];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (lane + 64 * i < nchunk) {
-        float xv[8], rv[8];
-        unpack8(xraw[rr][i], xv);
-        unpack8(rraw[rr][i], rv);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { xv[j] += rv[j]; h[i][j] = xv[j]; s += xv[j]; }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[i][j] = 0.f;
-      }
-    }
-    const float mean = wave_sum(s) / K;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (lane + 64 * i < nchunk) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float dd = h[i][j] - mean; q += dd * dd; }
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / K + eps);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ch = lane + 64 * i;
-      if (ch < nchunk) {
-        float y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = (h[i][j] - mean) * rstd * gam[i][j] + bet[i][j];
-        const u32x4 packed = (u32x4){pack2bf(y[0], y[1]), pack2bf(y[2], y[3]), pack2bf(y[4], y[5]), pack2bf(y[6], y[7])};
-        *(u32x4*)(xs + (size_t)m * K + ch * 8) = packed;
-        if (write_h) cst(packed, hnew, (unsigned)(m * K + ch * 8) * 2u);
-      }
-    }
   }
 }
 
@@ -414,14 +115,14 @@ __device__ __forceinline__ float wave_max_fast(float v) {
 #undef VAC_DPP
 
 // ---- single-query attention of one (row, head) pair (attn_decode_kernel's arithmetic) -------------------------------------
-// q: 64 bf16 at qoff of qrs (coherent).  Keys / values: rows j = 0..Tk-1 at koff + j * ldb / voff + j * ldb of kvrs (AUX = COH
-// for the self-attention cache, whose newest row was written in this launch; 0 for the static cross-attention K/V).
+// q: 64 bf16 at qoff of qrs (coherent) unless an.qlds.  Keys / values: rows j = 0..Tk-1 at koff + j * ldb / voff + j * ldb of kvrs,
+// loaded with the aux bits AUX (0: the cache rows and the cross-attention K/V are not written in this launch).
 // nw = 4 waves split the keys when Tk >= 256 (as the per-op path picks attn_decode_kernel<4>), else wave 0 alone.
 //
 // One wave's share [k_lo, k_hi) of the keys.  KU > 0: the share fits 64 * KU keys and EVERY load of the phase (q, the key rows,
 // the value rows) is issued before the first is consumed — the phase is a chain of dependent ~2 us round trips otherwise
 // (q -> keys -> values per 64 keys: 12 us for a 133-key share); the arithmetic and its order are unchanged.  KU == 0: any length.
-// (slot variant) qlds: the query as 64 bf16 in LDS instead of qrs; knew / vnew: the key / value row of position t_new in LDS — that
+// qlds: the query as 64 bf16 in LDS instead of qrs; knew / vnew: the key / value row of position t_new in LDS — that
 // row of the cache is being written by other workgroups in this launch and is not read.
 struct AttnNew { const bf16_t* qlds; const bf16_t* knew; const bf16_t* vnew; int t_new; bool fast; };     // fast: DPP wave reductions
 
@@ -646,171 +347,11 @@ __device__ __forceinline__ void attn_pair(rsrc_t qrs, unsigned qoff, rsrc_t kvrs
   }
 }
 
-__device__ __forceinline__ int wave_of(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
-
-#define TR(K_) do { if (p.trace && wg == p.trace_wg && tid == 0) p.trace[bar.ph * 8 + (K_)] = wall_clock64(); } while (0)
-#define END_PHASE(PREFETCH)                                     \
-  TR(3);                                                        \
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              \
-  TR(4);                                                        \
-  bar_arrive(bar);                                              \
-  { PREFETCH; }                                                 \
-  TR(5 - 8);                                                    \
-  if (!bar_wait(bar, &s_bad)) return;                           \
-  TR(0);
-
-__global__ __launch_bounds__(NTHR) void decoder_step_kernel(DecP p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* xs = (bf16_t*)smem;                                   // [R][max(d, F)] bf16
-  char* wbig = smem + p.xs_bytes + wave_of(threadIdx.x) * WBIG;                         // this wave's prefetch slots
-  char* wsml = smem + p.xs_bytes + NWAVE * WBIG + wave_of(threadIdx.x) * WSMALL;
-  float* lnp = (float*)(smem + p.xs_bytes + NWAVE * (WBIG + WSMALL));     // gamma[1024] | beta[1024] of the next LayerNorm
-  float* biasl = lnp + 2048;                                              // bias of this workgroup's (<= 16) output columns
-  float* probs = biasl + 64;                                              // [max(S, t + 1)] + 4 * 64 + 8
-  __shared__ float part[NWAVE][32];
-  __shared__ int s_bad;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int G = gridDim.x, wg = blockIdx.x;
-  const int R = p.R, d = p.d, F = p.F, H = p.H;
-  if (tid == 0) s_bad = 0;
-  Bar bar = {p.bar, G, 0u, false};
-
-  const unsigned act_b = (unsigned)(R * d * 2), f_b = (unsigned)(R * F * 2);
-  const rsrc_t rs_cache = mkrs(p.cache, p.cache_bytes);
-  const rsrc_t rs_h0 = mkrs(p.h0, act_b), rs_hb0 = mkrs(p.hb0, act_b), rs_hb1 = mkrs(p.hb1, act_b);
-  const rsrc_t rs_o = mkrs(p.o, act_b), rs_ctx = mkrs(p.ctx, act_b), rs_q = mkrs(p.q, act_b), rs_f = mkrs(p.f, f_b);
-  const OutD out_o = {rs_o, 0u, (unsigned)(d * 2)}, out_q = {rs_q, 0u, (unsigned)(d * 2)}, out_f = {rs_f, 0u, (unsigned)(F * 2)};
-  rsrc_t hcur = rs_h0;
-  int nln = 0;                                                  // LayerNorm k writes hb[k & 1]
-  const unsigned row_b = (unsigned)p.Tstride * 2u;              // bytes between two rows of one layer's cache
-  const int Tk_self = p.t + 1;
-
-  const unsigned wb_dd = (unsigned)(d * d * 2), wb_fd = (unsigned)(F * d * 2);
-  const int c1 = wg * NWAVE + wave, c4 = c1 * 4;               // this wave's first column in a 1- / 4-column-per-wave phase
-  // What is in flight across a barrier (issued between its arrive and its wait, retired inside the wait): the next projection's
-  // weight tile (per-wave slots), its bias values and, before a LayerNorm phase, gamma | beta (workgroup-shared slots).
-  {
-    const vacnic_decoder_layer l0 = p.layers[0];
-    w_issue<4>(wbig, mkrs(l0.w_kvq, 3 * wb_dd), 3 * d, d, c4, lane);
-    bias_issue(biasl, l0.b_kvq, 3 * d, wg * 16, 16, wave, lane);
-  }
-
-  for (int li = 0; li < p.L; ++li) {
-    const vacnic_decoder_layer ly = p.layers[li];
-    const unsigned lay_b = (unsigned)li * (unsigned)R * row_b;
-    // ---- P1: k|v|q of position t, in place in the cache (k|v at row t, q parked in the first d columns of row t + 1)
-    if (li == 0) {
-      stage_plain(rs_h0, xs, R, d, tid);
-      w_wait();
-    } else {
-      const rsrc_t hn = (nln & 1) ? rs_hb1 : rs_hb0;
-      stage_ln(rs_o, hcur, lnp, hn, wg == 0, xs, R, d, p.eps, wave, lane);
-      hcur = hn; ++nln;
-    }
-    __syncthreads();
-    TR(1);
-    {
-      const OutD out_c = {rs_cache, lay_b + (unsigned)p.t * (unsigned)(2 * d) * 2u, row_b};
-      gemv_phase<4>(wbig, mkrs(ly.w_kvq, 3 * wb_dd), ly.b_kvq, biasl, 3 * d, d, VACNIC_ACT_NONE, out_c, xs, R, G, wg, wave, lane);
-    }
-    END_PHASE(w_issue<1>(wsml, mkrs(ly.w_so, wb_dd), d, d, c1, lane); bias_issue(biasl, ly.b_so, d, wg * 4, 4, wave, lane))
-    // ---- P2: self-attention over cache rows 0..t
-    for (int pr = wg; pr < R * H; pr += G) {
-      const int r = pr / H, h = pr - r * H;
-      const unsigned rb = lay_b + (unsigned)r * row_b + (unsigned)h * 128u;
-      attn_pair<COH>(rs_cache, rb + (unsigned)(p.t + 1) * (unsigned)(2 * d) * 2u, rs_cache, rb, rb + (unsigned)d * 2u, (unsigned)(2 * d) * 2u,
-                     Tk_self, nullptr, p.scale, rs_ctx, (unsigned)(r * d + h * 64) * 2u, probs, wave, lane);
-      __syncthreads();
-    }
-    END_PHASE()
-    // ---- P3: self-attention output projection
-    stage_plain(rs_ctx, xs, R, d, tid);
-    __syncthreads();
-    TR(1);
-    gemv_phase<1>(wsml, mkrs(ly.w_so, wb_dd), ly.b_so, biasl, d, d, VACNIC_ACT_NONE, out_o, xs, R, G, wg, wave, lane);
-    END_PHASE(w_issue<1>(wsml, mkrs(ly.w_cq, wb_dd), d, d, c1, lane); bias_issue(biasl, ly.b_cq, d, wg * 4, 4, wave, lane);
-              ln_issue(lnp, ly.ln_self_g, ly.ln_self_b, d, wave, lane))
-    // ---- P4: post-LN of the self-attention block, cross-attention query
-    {
-      const rsrc_t hn = (nln & 1) ? rs_hb1 : rs_hb0;
-      stage_ln(rs_o, hcur, lnp, hn, wg == 0, xs, R, d, p.eps, wave, lane);
-      hcur = hn; ++nln;
-    }
-    __syncthreads();
-    TR(1);
-    gemv_phase<1>(wsml, mkrs(ly.w_cq, wb_dd), ly.b_cq, biasl, d, d, VACNIC_ACT_NONE, out_q, xs, R, G, wg, wave, lane);
-    END_PHASE(w_issue<1>(wsml, mkrs(ly.w_co, wb_dd), d, d, c1, lane); bias_issue(biasl, ly.b_co, d, wg * 4, 4, wave, lane))
-    // ---- P5: cross-attention over the encoder K/V
-    {
-      const unsigned kv_rows = ly.cross_bs == 0 ? 1u : (unsigned)R;
-      const rsrc_t rs_kv = mkrs(ly.cross_kv, kv_rows * (unsigned)p.S * (unsigned)(2 * d) * 2u);
-      for (int pr = wg; pr < R * H; pr += G) {
-        const int r = pr / H, h = pr - r * H;
-        const unsigned kb = (unsigned)r * (unsigned)ly.cross_bs * 2u + (unsigned)h * 128u;
-        attn_pair<0>(rs_q, (unsigned)(r * d + h * 64) * 2u, rs_kv, kb, kb + (unsigned)d * 2u, (unsigned)(2 * d) * 2u, p.S,
-                     p.enc_mask ? p.enc_mask + (size_t)r * p.S : nullptr, p.scale, rs_ctx, (unsigned)(r * d + h * 64) * 2u, probs, wave, lane);
-        __syncthreads();
-      }
-    }
-    END_PHASE()
-    // ---- P6: cross-attention output projection
-    stage_plain(rs_ctx, xs, R, d, tid);
-    __syncthreads();
-    TR(1);
-    gemv_phase<1>(wsml, mkrs(ly.w_co, wb_dd), ly.b_co, biasl, d, d, VACNIC_ACT_NONE, out_o, xs, R, G, wg, wave, lane);
-    END_PHASE(w_issue<4>(wbig, mkrs(ly.w_fc1, wb_fd), F, d, c4, lane); bias_issue(biasl, ly.b_fc1, F, wg * 16, 16, wave, lane);
-              ln_issue(lnp, ly.ln_cross_g, ly.ln_cross_b, d, wave, lane))
-    // ---- P7: post-LN of the cross-attention block, fc1 + GELU
-    {
-      const rsrc_t hn = (nln & 1) ? rs_hb1 : rs_hb0;
-      stage_ln(rs_o, hcur, lnp, hn, wg == 0, xs, R, d, p.eps, wave, lane);
-      hcur = hn; ++nln;
-    }
-    __syncthreads();
-    TR(1);
-    gemv_phase<4>(wbig, mkrs(ly.w_fc1, wb_fd), ly.b_fc1, biasl, F, d, VACNIC_ACT_GELU, out_f, xs, R, G, wg, wave, lane);
-    END_PHASE(w2_issue(wbig, mkrs(ly.w_fc2, wb_fd), d, F, wg * 4, wave, lane); bias_issue(biasl, ly.b_fc2, d, wg * 4, 4, wave, lane))
-    // ---- P8: fc2
-    stage_plain(rs_f, xs, R, F, tid);
-    __syncthreads();
-    TR(1);
-    gemv2_phase(wbig, mkrs(ly.w_fc2, wb_fd), ly.b_fc2, biasl, d, F, out_o, xs, R, G, wg, wave, lane, part);
-    if (li + 1 < p.L) {
-      const vacnic_decoder_layer nx = p.layers[li + 1];
-      END_PHASE(w_issue<4>(wbig, mkrs(nx.w_kvq, 3 * wb_dd), 3 * d, d, c4, lane); bias_issue(biasl, nx.b_kvq, 3 * d, wg * 16, 16, wave, lane);
-                ln_issue(lnp, ly.ln_final_g, ly.ln_final_b, d, wave, lane))
-    }
-  }
-  // exit: the last workgroup out clears the barrier state (stream order makes it visible to the next launch)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    if (__hip_atomic_fetch_add(p.bar + BAR_EXIT, 1u, __ATOMIC_RELAXED, AGENT) == (unsigned)G - 1) {
-      for (int i = 0; i < NGRP; ++i) __hip_atomic_store(p.bar + 32 * i, 0u, __ATOMIC_RELAXED, AGENT);
-      __hip_atomic_store(p.bar + BAR_TOP, 0u, __ATOMIC_RELAXED, AGENT);
-      for (int f = 0; f < NFLAG; ++f) __hip_atomic_store(p.bar + BAR_FLAG + 32 * f, 0u, __ATOMIC_RELAXED, AGENT);
-      __hip_atomic_store(p.bar + BAR_EXIT, 0u, __ATOMIC_RELAXED, AGENT);
-    }
-  }
-}
-
-
-// =====================================================================================================================
-// Slot variant (the default): no barriers at all.  A phase's producers hand their results to the consumers through TAGGED
-// SLOTS in HBM: a slot is a run of 16-byte units {6 bf16 values, 32-bit tag}, written with one coherent 16-byte store per unit
-// and NO wait for the acknowledgement; a consumer thread polls "its" producer's slot until every unit carries the tag of
-// (this launch, this phase) and scatters the values into the workgroup's LDS copy of the activation.  The data IS the
-// signal, so a phase boundary costs one store-to-visible latency plus one poll round trip (~1.5 us) instead of store
-// acknowledgement + two dependent atomics + flag poll + reload (~4 us with the barrier).  Tag = nonce * 1024 + phase, nonce =
-// a per-buffer launch counter (read by everybody at the start, bumped by workgroup 0 at its exit — which cannot happen before
-// every workgroup has produced its last phase), so a stale slot can never match.  A slot array is reused once per layer:
-// whoever produces phase X of layer l+1 has consumed data that transitively required every workgroup to be past its read of
-// (l, X).  The residual stream h never leaves the chip: every workgroup normalises all rows anyway and keeps h in LDS.
-//   slot arrays (bytes): 6 GEMV outputs x 256 workgroups x 384  |  2 attention outputs x 128 (row, head) pairs x 192
+// ---- tagged slots (see the head of the file) ----------------------------------------------------------------------------
+// slot arrays (bytes): 6 GEMV outputs x 256 workgroups x 384  |  2 attention outputs x 128 (row, head) pairs x 192  |  fc1 per layer
 constexpr unsigned SLOT_STRIDE = 384, CTX_STRIDE = 192, SLOT_ARR = 256 * SLOT_STRIDE, CTX_ARR0 = 6 * SLOT_ARR, CTX_ARR = 128 * CTX_STRIDE;
 constexpr unsigned FC1L_ARR0 = CTX_ARR0 + 2 * CTX_ARR;      // + layer * SLOT_ARR: the fc1 outputs get one array PER LAYER (see gather_cols)
 constexpr int MAX_L = 120;
-constexpr int BAR_NONCE = BAR_ERR + 32;
 enum { A_KVQ = 0, A_SO = 1, A_CQ = 2, A_CO = 3, A_FC1 = 4, A_FC2 = 5 };
 
 struct PollCtx { unsigned* errw; int* s_bad; };
@@ -911,7 +452,7 @@ __device__ __forceinline__ void slot_put(rsrc_t srs, unsigned off, const unsigne
   }
 }
 
-// ---- slot variant: MFMA projections ------------------------------------------------------------------------------------
+// ---- MFMA projections ------------------------------------------------------------------------------------------------
 // A workgroup's output tile is NC = 16 (k|v|q, fc1) or 4 (d-wide projections, fc2) weight rows x all activation rows; one
 // v_mfma_f32_16x16x32_bf16 multiplies 16 weight rows by 16 activation rows (R valid, the rest zero) over 32 k, the 4 waves split
 // K and meet in LDS.  ~0.3 us instead of ~500-1000 VALU instructions per wave (1.5-3 us with one wave per SIMD).  The weight
@@ -1210,17 +751,16 @@ extern "C" int64_t vacnic_decoder_step_slots_bytes(int64_t L) { return (int64_t)
 
 extern "C" int vacnic_decoder_step(const vacnic_decoder_step_args* a, void* stream) {
   VPLAN_REC_STRUCT(vacnic_decoder_step, a, stream);
-  VCHECK(a && a->layers && a->cache && a->h0 && a->hbuf[0] && a->hbuf[1] && a->obuf && a->ctx && a->qbuf && a->fbuf && a->sync,
-         VACNIC_BAD_SHAPE, "decoder_step: null operand");
-  VCHECK(a->L >= 1 && a->R >= 1 && a->R <= MR, VACNIC_UNSUPPORTED, "decoder_step: 1 <= R <= 8 rows (beams x batch), L >= 1");
-  VCHECK(a->d >= 64 && a->d <= 1024 && (a->d & 7) == 0 && a->H * 64 == a->d, VACNIC_UNSUPPORTED,
-         "decoder_step: d_model <= 1024, multiple of 8, heads of 64");
-  VCHECK(a->F >= 8 && a->F <= 4096 && (a->F & 7) == 0, VACNIC_UNSUPPORTED, "decoder_step: ffn_dim <= 4096, multiple of 8");
+  VCHECK(a && a->layers && a->cache && a->h0 && a->obuf && a->sync && a->slots, VACNIC_BAD_SHAPE, "decoder_step: null operand");
+  VCHECK(a->L >= 1 && a->L <= MAX_L && a->R >= 1 && a->R <= MR, VACNIC_UNSUPPORTED, "decoder_step: 1 <= R <= 8 rows (beams x batch), 1 <= L <= 120");
+  VCHECK(a->d >= 64 && a->d <= 1024 && (a->d & 15) == 0 && a->H * 64 == a->d, VACNIC_UNSUPPORTED,
+         "decoder_step: d_model <= 1024, multiple of 16, heads of 64");
+  VCHECK(a->F >= 16 && a->F <= 4096 && (a->F & 15) == 0, VACNIC_UNSUPPORTED, "decoder_step: ffn_dim <= 4096, multiple of 16");
   VCHECK(a->S >= 1 && a->S <= 8192 && a->t >= 0 && a->t < a->Tmax && a->Tmax <= 8191, VACNIC_BAD_SHAPE, "decoder_step: 0 <= t < Tmax, 1 <= S <= 8192");
   const int64_t cache_bytes = a->L * a->R * (a->Tmax + 1) * 2 * a->d * 2;
   VCHECK(cache_bytes < ((int64_t)1 << 31) && a->R * a->S * 2 * a->d * 2 < ((int64_t)1 << 31), VACNIC_UNSUPPORTED, "decoder_step: cache beyond 2 GiB");
-  VCHECK(aligned16(a->cache) && aligned16(a->h0) && aligned16(a->hbuf[0]) && aligned16(a->hbuf[1]) && aligned16(a->obuf) && aligned16(a->ctx) &&
-         aligned16(a->qbuf) && aligned16(a->fbuf), VACNIC_MISALIGNED, "decoder_step: 16-byte aligned buffers");
+  VCHECK(aligned16(a->cache) && aligned16(a->h0) && aligned16(a->obuf) && aligned16(a->slots), VACNIC_MISALIGNED,
+         "decoder_step: 16-byte aligned buffers");
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0, v = 0;
@@ -1230,49 +770,35 @@ extern "C" int vacnic_decoder_step(const vacnic_decoder_step_args* a, void* stre
     }
     n_cu = v;
   }
+  // one workgroup per 4 columns of a d-wide projection / 16 columns of the FFN: every launched workgroup produces in the last
+  // layer's fc1 or fc2, both consumed by workgroup 0 before it bumps the launch nonce
+  const int64_t G = a->d / 4 > a->F / 16 ? a->d / 4 : a->F / 16;
+  VCHECK(G <= 256 && G <= n_cu && a->R * a->H <= 128 && a->R * a->H <= G, VACNIC_UNSUPPORTED,
+         "decoder_step: needs max(d / 4, ffn / 16) <= min(256, CUs) co-resident workgroups and R * H <= that count");
   DecP p;
-  p.layers = a->layers; p.cache = (bf16_t*)a->cache; p.h0 = (const bf16_t*)a->h0;
-  p.hb0 = (bf16_t*)a->hbuf[0]; p.hb1 = (bf16_t*)a->hbuf[1]; p.o = (bf16_t*)a->obuf; p.ctx = (bf16_t*)a->ctx; p.q = (bf16_t*)a->qbuf;
-  p.f = (bf16_t*)a->fbuf; p.enc_mask = a->enc_mask; p.bar = a->sync;
+  p.layers = a->layers; p.cache = (bf16_t*)a->cache; p.h0 = (const bf16_t*)a->h0; p.o = (bf16_t*)a->obuf;
+  p.enc_mask = a->enc_mask; p.bar = a->sync;
   p.L = (int)a->L; p.R = (int)a->R; p.d = (int)a->d; p.H = (int)a->H; p.F = (int)a->F; p.S = (int)a->S; p.t = (int)a->t;
   p.Tstride = (int)((a->Tmax + 1) * 2 * a->d);
   p.cache_bytes = (unsigned)cache_bytes;
   const int64_t kmax = a->d > a->F ? a->d : a->F;
-  p.xs_bytes = (unsigned)(a->R * kmax * 2);
+  p.xs_bytes = (unsigned)(a->R * (kmax + 8) * 2);
   p.eps = a->eps; p.scale = a->scale;
   p.trace = (unsigned long long*)a->trace; p.trace_wg = (int)a->trace_wg;
   p.slots = (char*)a->slots;
   const int64_t tkmax = a->S > a->t + 1 ? a->S : a->t + 1;
-  const bool use_slots = a->slots != nullptr;
-  size_t lds = (size_t)p.xs_bytes + (size_t)NWAVE * (WBIG + WSMALL) + (size_t)(2048 + 64) * 4 + (size_t)(tkmax + NWAVE * 64 + 8) * 4;
-  if (use_slots) {
-    p.xs_bytes = (unsigned)(a->R * (kmax + 8) * 2);
-    lds = (size_t)p.xs_bytes + (size_t)NWAVE * (WBIG + WSMALL) + (size_t)(2048 + 64) * 4 + (size_t)MR * 1024 * 2 + 160 * 2 + 192 * 2 + 1024 * 4 +
-          (size_t)(tkmax + NWAVE * 64 + 8) * 4;
-  }
+  const size_t lds = (size_t)p.xs_bytes + (size_t)NWAVE * (WBIG + WSMALL) + (size_t)(2048 + 64) * 4 + (size_t)MR * 1024 * 2 + 160 * 2 + 192 * 2 +
+                     1024 * 4 + (size_t)(tkmax + NWAVE * 64 + 8) * 4;
   VCHECK(lds <= 150 * 1024, VACNIC_UNSUPPORTED, "decoder_step: LDS budget");
-  static bool lds_set[2] = {false, false};
-  if (lds > 65536 - 1024 && !lds_set[use_slots]) {
-    const void* fn = use_slots ? (const void*)decoder_step_slots_kernel : (const void*)decoder_step_kernel;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(150 * 1024)) != hipSuccess) {
+  static bool lds_set = false;
+  if (lds > 65536 - 1024 && !lds_set) {
+    if (hipFuncSetAttribute((const void*)decoder_step_slots_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(150 * 1024)) != hipSuccess) {
       vacnic_set_error("decoder_step: cannot raise the dynamic LDS limit");
       return VACNIC_HIP_ERROR;
     }
-    lds_set[use_slots] = true;
+    lds_set = true;
   }
-  if (use_slots) {
-    // one workgroup per 4 columns of a d-wide projection / 16 columns of the FFN: every launched workgroup produces in the last
-    // layer's fc1 or fc2, both consumed by workgroup 0 before it bumps the launch nonce
-    VCHECK((a->d & 15) == 0 && (a->F & 15) == 0 && a->L <= MAX_L, VACNIC_UNSUPPORTED, "decoder_step (slots): d, F multiples of 16, L <= 120");
-    const int64_t G = a->d / 4 > a->F / 16 ? a->d / 4 : a->F / 16;
-    VCHECK(G <= 256 && G <= n_cu && a->R * a->H <= 128 && a->R * a->H <= G, VACNIC_UNSUPPORTED,
-           "decoder_step (slots): needs max(d / 4, ffn / 16) <= min(256, CUs) co-resident workgroups");
-    VCHECK(aligned16(a->slots), VACNIC_MISALIGNED, "decoder_step: slots must be 16-byte aligned");
-    hipLaunchKernelGGL(decoder_step_slots_kernel, dim3((unsigned)G), dim3(NTHR), lds, (hipStream_t)stream, p);
-  } else {
-    const int G = n_cu < 256 ? n_cu : 256;
-    hipLaunchKernelGGL(decoder_step_kernel, dim3(G), dim3(NTHR), lds, (hipStream_t)stream, p);
-  }
+  hipLaunchKernelGGL(decoder_step_slots_kernel, dim3((unsigned)G), dim3(NTHR), lds, (hipStream_t)stream, p);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

@@ -135,27 +135,23 @@ class CachedDecoder:
         self.cross_all = torch.empty((self.L, rows, S, 2 * d), device=dev, dtype=BF16)      # one block: a staged caption arrives in one copy
         self.cross = [self.cross_all[li] for li in range(self.L)]
         self.lidx = (torch.arange(self.L, device=dev)[:, None] * rows).contiguous()
-        # persistent decoder-step kernel (vacnic_decoder_step): all layers of a position in one launch.  VACNIC_DECODE_PER_OP=1
-        # keeps the kernel-per-op chain (the reference the step kernel is tested against).
+        # persistent decoder-step kernel (vacnic_decoder_step): all layers of a position in one launch, G = max(d/4, F/16)
+        # co-resident workgroups exchanging through tagged slots.  Every other shape, and VACNIC_DECODE_PER_OP=1, takes the
+        # kernel-per-op chain (the reference the step kernel is tested against).
         F = dec.layers[0].fc1.weight.shape[0]
         self.F = F
-        self.step_kernel = (os.environ.get("VACNIC_DECODE_PER_OP", "0") != "1" and rows <= 8 and d <= 1024 and d % 8 == 0 and F <= 4096
-                            and F % 8 == 0 and self.H * 64 == d and max_length <= 8191)
+        G = max(d // 4, F // 16)
+        self.step_kernel = (os.environ.get("VACNIC_DECODE_PER_OP", "0") != "1" and rows <= 8 and d <= 1024 and d % 16 == 0 and F <= 4096
+                            and F % 16 == 0 and self.H * 64 == d and max_length <= 8191 and self.L <= 120 and rows * self.H <= min(128, G)
+                            and G <= min(256, torch.cuda.get_device_properties(dev).multi_processor_count))
         self.step_table = None
         self.trace, self.trace_wg = None, 0       # tools/decstep_trace.py: per-phase time stamps of one workgroup
         self.last_hidden = None
+        self.slots = None
         if self.step_kernel:
             self.sync = torch.zeros(int(_lib.lib.vacnic_decoder_step_sync_bytes()) // 4, device=dev, dtype=torch.int32)
-            # tagged-slot exchange (no grid barriers) when the workgroup count fits the GPU; VACNIC_DECODE_BARRIER=1: barrier variant
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            G = max(d // 4, F // 16)
-            self.slots = None
-            if (os.environ.get("VACNIC_DECODE_BARRIER", "0") != "1" and d % 16 == 0 and F % 16 == 0 and G <= min(256, cus)
-                    and rows * self.H <= min(128, G) and self.L <= 120):
-                self.slots = torch.zeros(int(_lib.lib.vacnic_decoder_step_slots_bytes(self.L)), device=dev, dtype=torch.uint8)
-            self.hbuf = [torch.zeros((rows, d), device=dev, dtype=BF16) for _ in range(2)]
-            self.obuf, self.ctxb, self.qbuf = (torch.zeros((rows, d), device=dev, dtype=BF16) for _ in range(3))
-            self.fbuf = torch.zeros((rows, F), device=dev, dtype=BF16)
+            self.slots = torch.zeros(int(_lib.lib.vacnic_decoder_step_slots_bytes(self.L)), device=dev, dtype=torch.uint8)
+            self.obuf = torch.zeros((rows, d), device=dev, dtype=BF16)
 
     def begin(self, enc_h, mask_u8, nb):
         """expand the encoder states to beams (HF _expand_inputs_for_generation: row b*nb + j <- batch b) and compute the
@@ -212,25 +208,24 @@ class CachedDecoder:
         return self.step_table[0]
 
     def _step_all_layers(self, h, t):
-        """every decoder layer of position t in one launch; returns the last layer's (block output, residual) pair."""
+        """every decoder layer of position t in one launch; returns the decoder's final hidden rows [rows, d] (after the last
+        layer's LayerNorm)."""
         lay = self.dec.layers[0]
         _lib.call_struct("vacnic_decoder_step", stream=K._stream(), layers=self._layer_table().data_ptr(), cache=self.cache_at(t).data_ptr(),
-                         h0=h.data_ptr(), hbuf0=self.hbuf[0].data_ptr(), hbuf1=self.hbuf[1].data_ptr(), obuf=self.obuf.data_ptr(),
-                         ctx=self.ctxb.data_ptr(), qbuf=self.qbuf.data_ptr(), fbuf=self.fbuf.data_ptr(), enc_mask=self.enc_mask.data_ptr(),
-                         sync=self.sync.data_ptr(), slots=self.slots.data_ptr() if self.slots is not None else None, L=self.L, R=self.rows, d=self.d, H=self.H, F=self.F, S=self.S, t=t, Tmax=self.Tmax,
+                         h0=h.data_ptr(), obuf=self.obuf.data_ptr(), enc_mask=self.enc_mask.data_ptr(), sync=self.sync.data_ptr(),
+                         slots=self.slots.data_ptr(), L=self.L, R=self.rows, d=self.d, H=self.H, F=self.F, S=self.S, t=t, Tmax=self.Tmax,
                          eps=lay.final_layer_norm.eps, scale=0.125, trace=self.trace.data_ptr() if self.trace is not None else None,
                          trace_wg=self.trace_wg)
-        return self.obuf, self.hbuf[self.L & 1]
+        return self.obuf
 
     def check_step_kernel(self):
-        """after the results were read back: did a grid barrier of the step kernel time out?"""
+        """after the results were read back: did a wait of the step kernel for another workgroup's slot time out?"""
         if self.step_kernel and int(self.sync[-64].item()) != 0:
-            # a timed-out launch left the barrier counters / nonce and (slot variant) units tagged with the aborted nonce behind:
-            # clear BOTH, so that a later launch can never match stale tags, and take this decoder off the step kernel — whoever
-            # keeps using it (a cached DecodeSession) continues on the kernel-per-op chain
+            # a timed-out launch left the error word, the launch nonce and units tagged with that nonce behind: clear BOTH buffers,
+            # so that a later launch can never match stale tags, and take this decoder off the step kernel — whoever keeps using
+            # it (a cached DecodeSession) continues on the kernel-per-op chain
             self.sync.zero_()
-            if self.slots is not None:
-                self.slots.zero_()
+            self.slots.zero_()
             self.step_kernel = False
             self.step_table = None
             raise RuntimeError("vacnic_decoder_step: a wait inside the step kernel timed out (workgroups not co-resident?); results of "
@@ -243,6 +238,14 @@ class CachedDecoder:
         ln = dec.layernorm_embedding
         h, _, _ = K.embed_ln_fwd(ids_t, dec.embed_tokens.weight.w16, dec.embed_positions.weight.w16, ln.weight.data, ln.bias.data,
                                  embed_scale=dec.embed_scale, pos_offset=2 + t)
+        if self.step_kernel:
+            hn = self._step_all_layers(h.view(R, d), t)
+            self.last_hidden = hn
+            if hidden_only:
+                return hn
+            logits = torch.empty((R, m.V_pad), device=h.device, dtype=torch.float32)
+            K.gemm(hn, m.emb16_pad, R, m.V, d, bias=m.final_logits_bias.view(-1), out=logits, ldo=m.V_pad, out_mode=1)
+            return logits
         cache = self.cache_at(t)
         # R <= 8 rows (one caption, <= 8 beams): every post-LN (residual add + LayerNorm) rides as a prologue on the projection
         # that consumes it (vacnic_gemv_ln_bf16) — 36 fewer launches per token, bit-identical values.  `pend` = the block output
@@ -257,10 +260,7 @@ class CachedDecoder:
                           ldw=w.stride(0), ldo=ldo, act=act, out_mode=out_mode, eps=lnm.eps)
             return y, hn
 
-        if self.step_kernel:
-            pend = self._step_all_layers(h.view(R, d), t)
-            pend_ln = dec.layers[-1].final_layer_norm
-        for li, layer in enumerate(dec.layers if not self.step_kernel else ()):
+        for li, layer in enumerate(dec.layers):
             a = layer.self_attn
             row = cache[li][:, t]                                                               # [R, 2d] view, row stride (Tmax+1)*2d
             if pend is None:
@@ -295,9 +295,7 @@ class CachedDecoder:
             else:
                 h, _, _ = K.add_ln_fwd(o.view(R, 1, d), h, layer.final_layer_norm.weight.data, layer.final_layer_norm.bias.data, need_stats=False)
         if hidden_only:
-            if self.step_kernel and self.slots is not None:
-                self.last_hidden = pend[0]
-            elif fuse and pend is not None:
+            if fuse and pend is not None:
                 o_, res_ = pend
                 hn, _, _ = K.add_ln_fwd(o_.view(R, 1, d), res_.view(R, 1, d), pend_ln.weight.data, pend_ln.bias.data, need_stats=False)
                 self.last_hidden = hn.view(R, d)
@@ -306,10 +304,7 @@ class CachedDecoder:
             return self.last_hidden
         logits = torch.empty((R, m.V_pad), device=h.device, dtype=torch.float32)
         # last_hidden: the final hidden rows [R, d] behind these logits (diagnostics / fixture construction; overwritten every step)
-        if self.step_kernel and self.slots is not None:     # slot variant: obuf already holds the final (normalised) hidden rows
-            K.gemm(pend[0], m.emb16_pad, R, m.V, d, bias=m.final_logits_bias.view(-1), out=logits, ldo=m.V_pad, out_mode=1)
-            self.last_hidden = pend[0]
-        elif fuse and pend is not None:
+        if fuse and pend is not None:
             _, self.last_hidden = ln_then(pend_ln, m.emb16_pad, m.V, m.final_logits_bias.view(-1), out=logits, ldo=m.V_pad, out_mode=1)
         else:
             K.gemm(h.view(R, d), m.emb16_pad, R, m.V, d, bias=m.final_logits_bias.view(-1), out=logits, ldo=m.V_pad, out_mode=1)
@@ -348,9 +343,9 @@ class DecodeSession:
         self.h_src = torch.zeros(R, dtype=torch.long).pin_memory()
         self.h_bans = torch.full((R, max_length), -1, dtype=torch.int32).pin_memory() if ngram > 0 else None
         self.graphs, self.outs, self.pool = {}, {}, None
-        # few rows (one caption's beams): the fused LM head + top-k (VACNIC_FUSED_LMHEAD_TOPK=0: skinny GEMM -> vacnic_beam_topk)
+        # few rows (one caption's beams): the fused LM head + top-k; other shapes: skinny GEMM -> vacnic_beam_topk
         self.fused_tail = (R <= 8 and model.emb16_pad.shape[1] <= 1024 and model.emb16_pad.shape[1] % 8 == 0 and min(2 * nb, model.V) <= 64
-                           and model.V <= 512 * 128 and os.environ.get("VACNIC_FUSED_LMHEAD_TOPK", "1") != "0")
+                           and model.V <= 512 * 128)
         self.captions = 0
         self.beam = None                  # device-side beam bookkeeping (enable_device_beams)
 
