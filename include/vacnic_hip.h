@@ -172,6 +172,26 @@ typedef struct {
 int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream);
 
 /*
+ * Attention probabilities (output_attentions=True): the attn_weights_reshaped of BartAttention.forward, MFULL:509-544 —
+ *   out[b][h][i][j] = softmax_j( scale * q[b][i][h*64..] . k[b][j][h*64..] + masks ),  fp32 [B][H][Tq][Tk], contiguous,
+ * the softmax BEFORE dropout (MFULL:534 vs :546), in train and eval mode alike.  q / k / key_mask / causal / scale exactly as
+ * in vacnic_attn_fwd (the fused k|v|q and k|v buffers are passed as strided views); H*64 must fit both row strides.
+ * Masked keys and the causal upper triangle come out as exactly 0.0; a row whose keys are all masked is uniform 1/Tk, as torch
+ * gives it for the additive finfo.min mask.  Independent of vacnic_attn_fwd's lse (two sweeps over the keys); every element has
+ * one writer and a fixed summation order, so two launches give identical bits.  Tk <= 4096 (VACNIC_UNSUPPORTED beyond: the key
+ * bias of a row lives in LDS); one Tq x Tk map must stay below 2 GiB.
+ */
+typedef struct {
+  const void* q; const void* k; float* out;
+  const uint8_t* key_mask;
+  int64_t B, H, Tq, Tk;
+  int64_t ldq, ldk;
+  int64_t bsq, bsk;               /* batch strides in elements */
+  int32_t causal; float scale;
+} vacnic_attn_probs_args;
+int vacnic_attn_probs(const vacnic_attn_probs_args* a, void* stream);
+
+/*
  * out = LayerNorm(residual + dropout(x)) * gamma + beta   (post-LN blocks, MFULL:651-653,705-707,
  * 721-723,742-744; nn.LayerNorm eps=1e-5).  x/residual/out bf16 [R][D]; residual may be NULL
  * (plain LN: ViT ln_pre/ln_1/ln_2/ln_post, ner_map_layer_norm).  Dropout is Philox keyed on

@@ -64,6 +64,12 @@ AttnBwdArgs = _struct("vacnic_attn_bwd_args", [
     ("lddq", i64), ("lddk", i64), ("lddv", i64), ("bsdq", i64), ("bsdk", i64), ("bsdv", i64),
     ("causal", i32), ("scale", f32), ("p_drop", f32), ("seed", u64), ("seed_dev", vp)])
 
+AttnProbsArgs = _struct("vacnic_attn_probs_args", [
+    ("q", vp), ("k", vp), ("out", vp), ("key_mask", vp),
+    ("B", i64), ("H", i64), ("Tq", i64), ("Tk", i64),
+    ("ldq", i64), ("ldk", i64), ("bsq", i64), ("bsk", i64),
+    ("causal", i32), ("scale", f32)])
+
 AddLnFwdArgs = _struct("vacnic_add_ln_fwd_args", [
     ("x", vp), ("residual", vp), ("gamma", vp), ("beta", vp), ("out", vp), ("mean", vp), ("rstd", vp),
     ("R", i64), ("D", i64), ("eps", f32), ("p_drop", f32), ("seed", u64), ("seed_dev", vp)])
@@ -146,6 +152,7 @@ AdamwArgs = _struct("vacnic_adamw_args", [
 # (tests/test_abi.py parses the header and checks both directions).
 _STRUCT_FNS = {
     "vacnic_gemm_bf16": GemmArgs, "vacnic_gemv_ln_bf16": GemvLnArgs, "vacnic_attn_fwd": AttnFwdArgs, "vacnic_attn_bwd": AttnBwdArgs,
+    "vacnic_attn_probs": AttnProbsArgs,
     "vacnic_add_ln_fwd": AddLnFwdArgs, "vacnic_add_ln_bwd": AddLnBwdArgs,
     "vacnic_embed_ln_fwd": EmbedLnFwdArgs, "vacnic_embed_ln_bwd": EmbedLnBwdArgs,
     "vacnic_ce_fwd": CeArgs, "vacnic_ce_bwd": CeArgs,

@@ -38,6 +38,7 @@ class VacnicConfig:
     init_attn_weight: bool = False     # MFULL:1858-1870: tie name-self-attn / image-name cross-attn weights to the text self-attn
     face_dim: int = 512
     clip_width: int = 768              # input dim of the ClipCap MLP (hard-coded 768 at MFULL:1136; 1024 for ViT-L/14)
+    output_attentions: bool = False    # BartConfig.output_attentions: default of forward(output_attentions=None) (MFULL:1225,1533,1754)
 
     @property
     def head_dim(self):

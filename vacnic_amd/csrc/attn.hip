@@ -920,3 +920,221 @@ extern "C" int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream) {
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
+
+// =================================================================================================
+// attention probabilities (output_attentions): P = softmax(scale Q K^T + masks) as fp32 [B][H][Tq][Tk] — the
+// attn_weights_reshaped of MFULL:536-544, before dropout.  Independent of the forward kernel's lse (a fully masked row is not
+// recoverable from it: FMIN + log Tk absorbs in fp32), so two sweeps over the 64-key tiles: sweep 1 takes the row maximum and
+// row sum online, sweep 2 recomputes the tile, normalises and stores.  The kernel is store-bound (4 bytes out per MFMA'd score),
+// which decides its shape:
+//  - workgroup = 4 waves x 32 queries, query on the LANE as in the forward kernel (softmax state is a per-lane scalar);
+//  - the K tile goes HBM -> registers -> LDS (two buffers, one barrier per tile), NOT by LDS-DMA: the loads of the next tile are
+//    issued before this tile's stores and consumed after them, so the compiler's counted vmcnt waits for the loads alone and the
+//    stores stay in flight across the barrier (a DMA'd tile would need a hand-counted wait over loads and stores);
+//  - the accumulator layout gives a lane 4 consecutive keys of one query (32 rows x 32 bytes per wave-instruction), so each wave
+//    turns its 32 x 64 tile round in 8 KiB of LDS of its own and stores 4 rows x 256 contiguous bytes per instruction with
+//    16-byte lanes.  Rows of the contiguous output are 16-byte aligned only when Tk % 4 == 0; otherwise (VEC = false) the same
+//    segments go out as dwords;
+//  - all stores are buffer stores bounded to this (batch, head)'s Tq x Tk block, edge lanes get an out-of-range offset:
+//    no EXEC branches around them, and nothing can be written outside the block.
+// =================================================================================================
+struct ProbsP {
+  const bf16_t* q; const bf16_t* k; float* out; const uint8_t* key_mask;
+  int B, H, Tq, Tk, ldq, ldk;
+  long bsq, bsk;
+  int causal; float scale;
+};
+
+constexpr int PROBS_WAVE_B = 32 * 64 * 4;      // one wave's [32 queries][64 keys] fp32 tile
+
+// this thread's two 16-byte chunks of key tile t (row-contiguous: 8 lanes read one 128-byte row), zero past Tk
+__device__ __forceinline__ void probs_load_k(__amdgpu_buffer_rsrc_t ks, int t, int Tk, int ldk, int tid, u32x4 kr[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = i * 32 + (tid >> 3), gr = t * 64 + row;
+    kr[i] = __builtin_amdgcn_raw_buffer_load_b128(ks, gr < Tk ? (int)(((unsigned)gr * (unsigned)ldk + (unsigned)((tid & 7) * 8)) * 2u) : OOB, 0, 0);
+  }
+}
+// ... into a [64][64] bf16 LDS tile in the layout frag_row reads (16-byte chunks XOR-swizzled by the row)
+__device__ __forceinline__ void probs_put_k(char* tile, int tid, const u32x4 kr[2]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = i * 32 + (tid >> 3);
+    *(u32x4*)(tile + row * 128 + (((tid & 7) ^ swz(row)) << 4)) = kr[i];
+  }
+}
+
+// scaled + masked scores of tile t in the log2 domain: s[kb][4 g + e] belongs to key 64 t + 32 kb + 8 g + 4 hh + e, query qidx
+template <bool CAUSAL>
+__device__ __forceinline__ void probs_scores(const char* kt, const bf16x8 qf[4], const float* kbias, int t, int lane,
+                                             int qidx, float scale2, f32x16 s[2]) {
+  const int hh = lane >> 5;
+#pragma unroll
+  for (int kb2 = 0; kb2 < 2; ++kb2) {
+    s[kb2] = (f32x16)(0.f);
+#pragma unroll
+    for (int ks4 = 0; ks4 < 4; ++ks4)
+      s[kb2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(kt, kb2 * 32, ks4, lane), qf[ks4], s[kb2], 0, 0, 0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int kbase = t * 64 + kb2 * 32 + 8 * g + 4 * hh;
+      const f32x4 bias = *(const f32x4*)(kbias + kbase);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float v = fmaf(s[kb2][4 * g + e], scale2, bias[e]);
+        if (CAUSAL && (kbase + e) > qidx) v += FMIN;
+        s[kb2][4 * g + e] = v;
+      }
+    }
+  }
+}
+
+template <bool CAUSAL, bool VEC>
+__global__ __launch_bounds__(256, 2) void attn_probs_kernel(ProbsP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int b, hd, qblk;
+  xcd_order((p.Tq + 127) >> 7, p.H, p.B * p.H, qblk, hd, b);
+  const int q0 = qblk * 128 + wave * 32;
+  const int ql = lane & 31, hh = lane >> 5;
+  const int Tk_pad = (p.Tk + 63) & ~63;
+  char* ot = smem + wave * PROBS_WAVE_B;                    // this wave's transpose tile
+  char* kring = smem + 4 * PROBS_WAVE_B;                    // 2 x [64][64] bf16 K tiles
+  float* kbias = (float*)(kring + 2 * TILE_B);
+  // (a wave whose 32 queries all lie past Tq runs along: its Q fragments load as zeros and every one of its stores is out of
+  // range.  A branch around its work would join a path with stores and one without before each K hand-over, and the compiler
+  // then waits for vmcnt(0) — for the stores — at every tile of every wave)
+
+  __amdgpu_buffer_rsrc_t qs = make_rsrc(p.q + (long)b * p.bsq + hd * 64, p.Tq, p.ldq);
+  __amdgpu_buffer_rsrc_t ks = make_rsrc(p.k + (long)b * p.bsk + hd * 64, p.Tk, p.ldk);
+  float* ob = p.out + ((long)b * p.H + hd) * ((long)p.Tq * p.Tk);
+  __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc((void*)ob, 0, (unsigned)p.Tq * (unsigned)p.Tk * 4u, 0x00020000);
+  const float scale2 = p.scale * 1.4426950408889634f;     // v_exp_f32 is 2^x
+
+  u32x4 kr[2];
+  probs_load_k(ks, 0, p.Tk, p.ldk, tid, kr);
+  // per-key additive bias: 0 / FMIN (masked, as _expand_mask) / -inf (tile padding)
+  {
+    const uint8_t* mrow = p.key_mask ? p.key_mask + (long)b * p.Tk : nullptr;
+    for (int j = tid; j < Tk_pad; j += 256) kbias[j] = j >= p.Tk ? -INFINITY : (mrow && mrow[j] == 0) ? FMIN : 0.f;
+  }
+  const int qidx = q0 + ql;
+  bf16x8 qf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    qf[s] = gload8(qs, qidx < p.Tq ? (int)(((unsigned)qidx * (unsigned)p.ldq + 16u * s + 8u * hh) * 2u) : OOB);
+  probs_put_k(kring, tid, kr);
+  // vmcnt(0) as an s_waitcnt the compiler sees: Q is in registers before the loops, so no wait inside them has to cover it
+  // (a wait for a load issued before the loop would also wait for the previous tile's stores, which were issued after it)
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  lds_barrier();
+  asm volatile("" ::: "memory");
+
+  const int ntile = Tk_pad >> 6;
+  // ---- sweep 1: row maximum and row sum (online).  Tile 0 holds key 0, which the causal mask never hides, so the maximum is
+  // finite (>= FMIN) from the first tile on.
+  float m_run = -INFINITY, l_run = 0.f;
+  for (int t = 0; t < ntile; ++t) {
+    const char* kt = kring + (t & 1) * TILE_B;
+    probs_load_k(ks, t + 1 < ntile ? t + 1 : 0, p.Tk, p.ldk, tid, kr);         // the last one fetches tile 0 for sweep 2
+    asm volatile("" ::: "memory");          // keeps the loads up here: the scheduler otherwise sinks them to their use
+    {
+      f32x16 s[2];
+      probs_scores<CAUSAL>(kt, qf, kbias, t, lane, qidx, scale2, s);
+      float tmax = -INFINITY, psum = 0.f;
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, s[kb2][r]);
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      const float m_new = fmaxf(m_run, tmax);
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) psum += __builtin_amdgcn_exp2f(s[kb2][r] - m_new);
+      l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + psum;          // m_run = -inf on the first tile -> factor 0
+      m_run = m_new;
+    }
+    asm volatile("" ::: "memory");          // ... and the hand-over down here, behind the tile's arithmetic
+    probs_put_k(kring + ((t + 1) & 1) * TILE_B, tid, kr);
+    lds_barrier();
+    asm volatile("" ::: "memory");
+  }
+  const float inv = 1.f / (l_run + __shfl_xor(l_run, 32, 64));
+
+  // ---- sweep 2: recompute, normalise, turn the tile round in LDS, store whole row segments.  The K ring goes on where sweep 1
+  // left it: tile t of this sweep is in buffer (ntile + t) & 1.
+  for (int t = 0; t < ntile; ++t) {
+    const char* kt = kring + ((ntile + t) & 1) * TILE_B;
+    if (t + 1 < ntile) probs_load_k(ks, t + 1, p.Tk, p.ldk, tid, kr);        // uniform; nothing follows the last tile
+    asm volatile("" ::: "memory");
+    {
+      f32x16 s[2];
+      probs_scores<CAUSAL>(kt, qf, kbias, t, lane, qidx, scale2, s);
+      // [32 rows][256 B], 16-byte chunks XOR-swizzled by the row (conflict-free for the b128 write and the b128 read)
+#pragma unroll
+      for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 pr;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pr[e] = __builtin_amdgcn_exp2f(s[kb2][4 * g + e] - m_run) * inv;
+          const int c16 = kb2 * 8 + 2 * g + hh;
+          *(f32x4*)(ot + ql * 256 + ((c16 ^ (ql & 15)) << 4)) = pr;
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // wave-local: written and read by the same wave
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int row = 4 * i + (lane >> 4), c16 = lane & 15;
+        const int qrow = q0 + row, key = t * 64 + 4 * c16;
+        const f32x4 v = *(const f32x4*)(ot + row * 256 + ((c16 ^ (row & 15)) << 4));
+        const unsigned off = ((unsigned)qrow * (unsigned)p.Tk + (unsigned)key) * 4u;
+        if (VEC) {
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), os, (qrow < p.Tq && key < p.Tk) ? (int)off : OOB, 0, 0);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), os, (qrow < p.Tq && key + e < p.Tk) ? (int)(off + 4u * e) : OOB, 0, 0);
+        }
+      }
+    }
+    if (t + 1 < ntile) {                                          // uniform; the barrier also fences this wave's transpose tile
+      probs_put_k(kring + ((ntile + t + 1) & 1) * TILE_B, tid, kr);
+      lds_barrier();
+      asm volatile("" ::: "memory");
+    }
+  }
+}
+
+extern "C" int vacnic_attn_probs(const vacnic_attn_probs_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_attn_probs, a, stream);
+  VCHECK(a && a->q && a->k && a->out, VACNIC_BAD_SHAPE, "attn_probs: null operand");
+  if (int e = check_common(a->B, a->H, a->Tq, a->Tk, a->ldq, a->ldk, 8, 8, "attn_probs")) return e;
+  VCHECK(a->H * 64 <= a->ldq && a->H * 64 <= a->ldk, VACNIC_BAD_SHAPE, "attn_probs: H*64 = %ld columns do not fit the row strides ldq=%ld ldk=%ld",
+         (long)(a->H * 64), (long)a->ldq, (long)a->ldk);
+  VCHECK(a->Tk <= 4096, VACNIC_UNSUPPORTED, "attn_probs: Tk=%ld beyond 4096 (the key bias of a row lives in LDS)", (long)a->Tk);
+  VCHECK(a->Tq * a->Tk * 4 <= (int64_t)OOB, VACNIC_BAD_SHAPE, "attn_probs: one Tq x Tk map must stay below 2 GiB (Tq=%ld Tk=%ld)",
+         (long)a->Tq, (long)a->Tk);
+  VCHECK(aligned16(a->q) && aligned16(a->k) && !(a->bsq & 7) && !(a->bsk & 7) && !(((uintptr_t)a->out) & 3), VACNIC_MISALIGNED,
+         "attn_probs: q/k pointers and batch strides must be 16-byte aligned, out 4-byte aligned");
+  ProbsP p = {};
+  p.q = (const bf16_t*)a->q; p.k = (const bf16_t*)a->k; p.out = a->out; p.key_mask = a->key_mask;
+  p.B = (int)a->B; p.H = (int)a->H; p.Tq = (int)a->Tq; p.Tk = (int)a->Tk;
+  p.ldq = (int)a->ldq; p.ldk = (int)a->ldk; p.bsq = a->bsq; p.bsk = a->bsk;
+  p.causal = a->causal; p.scale = a->scale;
+  const int Tk_pad = (p.Tk + 63) & ~63;
+  const dim3 grid((unsigned)(((p.Tq + 127) / 128) * p.H * p.B));
+  const size_t lds = 4 * PROBS_WAVE_B + 2 * TILE_B + (size_t)Tk_pad * 4;   // the waves' transpose tiles + K ring + key bias
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = (p.Tk & 3) == 0 && aligned16(a->out);                   // every row of the contiguous output 16-byte aligned
+  if (p.causal) {
+    if (vec) hipLaunchKernelGGL((attn_probs_kernel<true, true>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((attn_probs_kernel<true, false>), grid, dim3(256), lds, st, p);
+  } else {
+    if (vec) hipLaunchKernelGGL((attn_probs_kernel<false, true>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((attn_probs_kernel<false, false>), grid, dim3(256), lds, st, p);
+  }
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}

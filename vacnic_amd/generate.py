@@ -475,7 +475,8 @@ def _run_encoder(model, use_graphs, add_ner_ffn, input_ids, mask_u8, image_featu
     """the encoder pass of one generate() call: a hipGraph per input signature (GraphedCall) unless use_graphs is off"""
     def run_encoder(ids, m8, img, nids, nmask, faces, fmask, add_ner_ffn=add_ner_ffn):
         return model.model.encoder(input_ids=ids, attention_mask=m8, image_features=img, name_ids=nids, name_mask=nmask,
-                                   face_features=faces, face_mask=fmask, add_ner_ffn=add_ner_ffn)["last_hidden_state"]
+                                   face_features=faces, face_mask=fmask, add_ner_ffn=add_ner_ffn,
+                                   output_attentions=False)["last_hidden_state"]      # no maps in decoding, whatever the config says
     if not use_graphs:
         return run_encoder(input_ids, mask_u8, image_features, name_ids, name_mask, face_features, face_mask)
     ge = model.__dict__.setdefault("_graphed_encoders", {})

@@ -300,6 +300,21 @@ def attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, key_mask=None, c
                 seed_dev=_p(seed_dev))
 
 
+def attn_probs(q, k, B, H, Tq, Tk, key_mask=None, causal=False, scale=0.125):
+    """softmax(scale q k^T + masks) as fp32 [B, H, Tq, Tk] (MFULL:509-544, before dropout) from the q / k views attn_fwd takes:
+    masked keys and the causal triangle exactly 0, a fully masked row uniform 1/Tk.  Plain tensor, no autograd graph."""
+    for name, t, T in (("q", q, Tq), ("k", k, Tk)):
+        if t.dtype != BF16 or t.dim() != 3 or t.stride(2) != 1 or t.shape[0] != B or t.shape[1] != T:
+            raise ValueError(f"attn_probs: {name} must be a bf16 [B={B}, T={T}, >= H*64] view with unit inner stride, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    if key_mask is not None and (key_mask.dtype != torch.uint8 or tuple(key_mask.shape) != (B, Tk) or not key_mask.is_contiguous()):
+        raise ValueError(f"attn_probs: key_mask must be a contiguous uint8 [B={B}, Tk={Tk}] tensor, got {key_mask.dtype} {tuple(key_mask.shape)}")
+    out = torch.empty((B, H, Tq, Tk), device=q.device, dtype=torch.float32)
+    call_struct("vacnic_attn_probs", stream=_stream(), q=_p(q), k=_p(k), out=_p(out), key_mask=_p(key_mask), B=B, H=H, Tq=Tq, Tk=Tk,
+                ldq=q.stride(1), ldk=k.stride(1), bsq=q.stride(0), bsk=k.stride(0), causal=int(causal), scale=scale)
+    return out
+
+
 # -------------------------------------------------------------------------------------------- LN family
 def add_ln_fwd(x, residual, gamma, beta, eps=1e-5, p_drop=0.0, seed=0, need_stats=True, seed_dev=None):
     D = x.shape[-1]

@@ -82,7 +82,12 @@ class BartLearnedPositionalEmbedding(nn.Embedding):
 class BartAttention(nn.Module):
     """MFULL:421-565.  forward(hidden_states, key_value_states=None, key_mask=None, causal=False) returns the
     out_proj output; the additive [B,1,T,S] mask of the reference is replaced by its generator: a per-key
-    uint8 mask (0 = masked with finfo.min) and a causal flag."""
+    uint8 mask (0 = masked with finfo.min) and a causal flag.
+
+    output_attentions=True appends the attention map (attn_weights_reshaped, MFULL:536-544): fp32 [B, H, Tq, Tk], the softmax
+    BEFORE dropout in train and eval mode alike, computed by vacnic_attn_probs from the very q / k the attention used.  It is a
+    plain tensor without an autograd graph — no gradient flows through it (the reference's map does carry one; none of its
+    trainers uses it)."""
 
     def __init__(self, embed_dim, num_heads, dropout=0.0, is_decoder=False, bias=True, cross_only=False):
         """cross_only: an attention that is only ever used with key_value_states (the decoder's encoder_attn): its k|v
@@ -123,17 +128,22 @@ class BartAttention(nn.Module):
         """fused k|v projection of a cross-attention source (MFULL:478-484)."""
         return ops.linear(key_value_states, self.k_proj.weight, self.s_kv)
 
-    def forward(self, hidden_states, key_value_states=None, key_mask=None, causal=False, kv=None, skip=False, bank=None, slot=0):
-        """kv: optional precomputed project_kv(key_value_states).  skip=True: returns (output, hidden_states) — the residual
-        branch of the block, whose gradient joins the input gradient inside the first projection's dgrad GEMM."""
+    def forward(self, hidden_states, key_value_states=None, key_mask=None, causal=False, kv=None, skip=False, bank=None, slot=0,
+                output_attentions=False):
+        """kv: optional precomputed project_kv(key_value_states).
+        skip=False: returns the output, or (output, map) with output_attentions=True.
+        skip=True: returns (output, hidden_states, map) — hidden_states is the residual branch of the block, whose gradient joins
+        the input gradient inside the first projection's dgrad GEMM; map is None unless output_attentions=True."""
         H = self.num_heads
         lin = ops.linear_skip if skip else ops.linear
-        res = None
+        res = probs = None
         if key_value_states is None and kv is None:
             kvq = lin(hidden_states, self.k_proj.weight, self.s_kvq)
             if skip:
                 kvq, res = kvq
             ctx = ops.self_attention(kvq, key_mask, causal, H, self.dropout, self.training)                 # MFULL:546
+            if output_attentions:
+                probs = self._attention_map(kvq[..., 2 * self.embed_dim:], kvq[..., :self.embed_dim], key_mask, causal)
         else:
             q = lin(hidden_states, self.q_proj.weight, self.s_q)
             if skip:
@@ -141,8 +151,18 @@ class BartAttention(nn.Module):
             if kv is None:
                 kv = self.project_kv(key_value_states)
             ctx = ops.cross_attention(q, kv, key_mask, H, bank, slot, self.dropout, self.training)
+            if output_attentions:
+                probs = self._attention_map(q, kv[..., :self.embed_dim], key_mask, False)
         out = ops.linear(ctx, self.out_proj.weight, self.s_out)
-        return (out, res) if skip else out
+        if skip:
+            return out, res, probs
+        return (out, probs) if output_attentions else out
+
+    def _attention_map(self, q, k, key_mask, causal):
+        """MFULL:509-544 for the q / k views the attention kernel just read (q unscaled: the kernel applies head_dim**-0.5)."""
+        with torch.no_grad():
+            return K.attn_probs(q.detach(), k.detach(), q.shape[0], self.num_heads, q.shape[1], k.shape[1], key_mask=key_mask,
+                                causal=causal, scale=0.125)
 
 
 class _Ffn(nn.Module):
@@ -195,10 +215,16 @@ class BartEncoderLayer(nn.Module):
         return ops.add_ln(x, res, ln.weight, ln.bias, self.dropout if drop else 0.0, self.training)
 
     def forward(self, hidden_states, key_mask, hidden_states_img=None, hidden_states_face=None, hidden_states_ner=None,
-                face_name_key_mask=None, add_ner_ffn=True, fused=True, on_branch=False):
+                face_name_key_mask=None, add_ner_ffn=True, fused=True, on_branch=False, output_attentions=False):
         """on_branch: the image / face / name inputs were produced on the branch stream by an earlier layer; the caller
-        (BartEncoder) hops the last layer's outputs back to the compute stream."""
+        (BartEncoder) hops the last layer's outputs back to the compute stream.
+        output_attentions=True appends a 3-tuple of fp32 maps to the outputs: the text self-attention [B,H,S,S] (MFULL:699,728,
+        754-755) and the two maps the reference computes and discards (MFULL:671,712) — names <- [faces ; names] [B,H,N,F+N] of
+        self_attn_img_name and text <- [image prompt ; name prefix] [B,H,S,P+NG] ([B,H,S,P] for only_image) of cross_attn_img_ner;
+        the last two are None in a layer that is not fused, the name map also for only_image."""
         h = hidden_states
+        oa = bool(output_attentions)
+        self_map = name_map = cross_map = None
         if fused:
             # The image / face / name branches (MFULL:647-691) are a dozen small kernels over 20-80 tokens per sample and are
             # independent of the text self-attention block of this layer; with side streams on (training only) they run on
@@ -241,7 +267,9 @@ class BartEncoderLayer(nn.Module):
                     ner_q, ner_r = ops.fork(hidden_states_ner)
                     ner_q, ner_k = ops.fork(ner_q)
                     kv_src = ops.cat_tokens(face_kv, ner_k)
-                    att = self.self_attn_img_name(ner_q, key_value_states=kv_src, key_mask=face_name_key_mask)
+                    att = self.self_attn_img_name(ner_q, key_value_states=kv_src, key_mask=face_name_key_mask, output_attentions=oa)
+                    if oa:
+                        att, name_map = att
                     hidden_states_ner = self._ln(att, ner_r, self.img_name_attn_layer_norm, drop=False)
                     ner_p, ner_out = ops.fork(hidden_states_ner)
                     # name-prefix FFN on the FLAT view [B, d, N] (reshape, not transpose; :682-688)
@@ -255,17 +283,19 @@ class BartEncoderLayer(nn.Module):
                 else:
                     kv, hidden_states_img = ops.fork(hidden_states_img)
                 kv = self.cross_attn_img_ner.project_kv(kv)        # k|v projection of the [img ; prefix] tokens: also off the text chain
-            a, r = self.self_attn(h, key_mask=key_mask, skip=True)
+            a, r, self_map = self.self_attn(h, key_mask=key_mask, skip=True, output_attentions=oa)
             h = self._ln(a, r, self.self_attn_layer_norm)                                          # :697-707
             if br is not None:
                 (kv,) = ops.stream_hop(br_raw, main_raw, kv)
-            a, r = self.cross_attn_img_ner(h, kv=kv, key_mask=None, skip=True)
+            a, r, cross_map = self.cross_attn_img_ner(h, kv=kv, key_mask=None, skip=True, output_attentions=oa)
             h = self._ln(a, r, self.img_ner_attn_layer_norm)                                       # :711-723
         else:
-            a, r = self.self_attn(h, key_mask=key_mask, skip=True)
+            a, r, self_map = self.self_attn(h, key_mask=key_mask, skip=True, output_attentions=oa)
             h = self._ln(a, r, self.self_attn_layer_norm)                                          # :726-736
         a, r = ops.mlp2_skip(h, self.fc1.weight, self.s_fc1, self.s_fc2, p_act=self.activation_dropout, training=self.training)   # :740
         h = self._ln(a, r, self.final_layer_norm)                                                  # :738-744
+        if oa:
+            return h, hidden_states_face, hidden_states_ner, hidden_states_img, (self_map, name_map, cross_map)
         return h, hidden_states_face, hidden_states_ner, hidden_states_img
 
 
@@ -291,13 +321,17 @@ class BartDecoderLayer(nn.Module):
     def _ln(self, x, res, ln):
         return ops.add_ln(x, res, ln.weight, ln.bias, self.dropout, self.training)
 
-    def forward(self, hidden_states, encoder_hidden_states, encoder_key_mask, kv=None, bank=None, slot=0):
-        a, r = self.self_attn(hidden_states, causal=hidden_states.shape[1] > 1, skip=True)
+    def forward(self, hidden_states, encoder_hidden_states, encoder_key_mask, kv=None, bank=None, slot=0, output_attentions=False):
+        """output_attentions=True: returns (hidden_states, self-attention map [B,H,T,T], cross-attention map [B,H,T,S]), MFULL:884-885."""
+        oa = bool(output_attentions)
+        a, r, self_map = self.self_attn(hidden_states, causal=hidden_states.shape[1] > 1, skip=True, output_attentions=oa)
         h = self._ln(a, r, self.self_attn_layer_norm)
-        a, r = self.encoder_attn(h, key_value_states=encoder_hidden_states, key_mask=encoder_key_mask, kv=kv, skip=True, bank=bank, slot=slot)
+        a, r, cross_map = self.encoder_attn(h, key_value_states=encoder_hidden_states, key_mask=encoder_key_mask, kv=kv, skip=True, bank=bank, slot=slot,
+                                      output_attentions=oa)
         h = self._ln(a, r, self.encoder_attn_layer_norm)
         a, r = ops.mlp2_skip(h, self.fc1.weight, self.s_fc1, self.s_fc2, p_act=self.activation_dropout, training=self.training)   # MFULL:874
-        return self._ln(a, r, self.final_layer_norm)
+        h = self._ln(a, r, self.final_layer_norm)
+        return (h, self_map, cross_map) if oa else h
 
 
 class BartEncoder(nn.Module):
@@ -343,9 +377,13 @@ class BartEncoder(nn.Module):
         return self.embed_tokens
 
     def forward(self, input_ids=None, attention_mask=None, image_features=None, name_ids=None, name_mask=None,
-                face_features=None, face_mask=None, add_ner_ffn=True, **unused):
+                face_features=None, face_mask=None, add_ner_ffn=True, output_attentions=None, **unused):
+        """output_attentions (None: config.output_attentions, MFULL:1225) adds one entry per layer to three tuples: `attentions`
+        (text self-attention), `name_face_attentions` and `img_ner_cross_attentions` (None for a layer that is not fused)."""
         if input_ids is None:
             raise ValueError("You have to specify either input_ids or inputs_embeds")
+        oa = bool(output_attentions if output_attentions is not None else self.config.output_attentions)
+        maps = []
         B, S = input_ids.shape
         key_mask = attention_mask.to(torch.uint8) if attention_mask.dtype != torch.uint8 else attention_mask
         ln = self.layernorm_embedding
@@ -371,8 +409,10 @@ class BartEncoder(nn.Module):
         on_branch = False
         for idx, layer in enumerate(self.layers):
             fused = idx in self.fusion_layer
-            h, face, ner, img = layer(h, key_mask, hidden_states_img=img, hidden_states_face=face, hidden_states_ner=ner,
-                                      face_name_key_mask=fn_mask, add_ner_ffn=add_ner_ffn, fused=fused, on_branch=on_branch)
+            h, face, ner, img, *m = layer(h, key_mask, hidden_states_img=img, hidden_states_face=face, hidden_states_ner=ner,
+                                          face_name_key_mask=fn_mask, add_ner_ffn=add_ner_ffn, fused=fused, on_branch=on_branch,
+                                          output_attentions=oa)
+            maps.extend(m)
             on_branch = on_branch or (fused and use_branch)
         if on_branch:                               # back to the compute stream (SECLA reads the face stream; TRAIN:326-330)
             outs = list(ops.stream_hop(streams.raw("branch"), K._stream(), *[t for t in (img, face, ner) if t is not None]))
@@ -381,7 +421,12 @@ class BartEncoder(nn.Module):
                 face = outs.pop(0)
             if ner is not None:
                 ner = outs.pop(0)
-        return {"last_hidden_state": h, "hidden_states_img": img, "hidden_states_ner": ner, "hidden_states_face": face}
+        out = {"last_hidden_state": h, "hidden_states_img": img, "hidden_states_ner": ner, "hidden_states_face": face}
+        if oa:
+            out["attentions"] = tuple(m[0] for m in maps)
+            out["name_face_attentions"] = tuple(m[1] for m in maps)
+            out["img_ner_cross_attentions"] = tuple(m[2] for m in maps)
+        return out
 
 
 class BartDecoder(nn.Module):
@@ -411,7 +456,11 @@ class BartDecoder(nn.Module):
         t = a.trainable
         self.s_kv_all = LinearSpec(a.fused(ws, "w16"), a.fused(bs, "f32"), a.fused(ws, "grad") if t else None, a.fused(bs, "grad") if t else None)
 
-    def forward(self, input_ids, encoder_hidden_states, encoder_attention_mask, output_hidden_states=True):
+    def forward(self, input_ids, encoder_hidden_states, encoder_attention_mask, output_hidden_states=True, output_attentions=None):
+        """output_attentions (None: config.output_attentions, MFULL:1533): returns (h, states, self-attention maps, cross-attention
+        maps), one fp32 map per layer (MFULL:1579-1580, 1647-1651), instead of (h, states)."""
+        oa = bool(output_attentions if output_attentions is not None else self.config.output_attentions)
+        self_maps, cross_maps = [], []
         ln = self.layernorm_embedding
         h = ops.embed_ln(input_ids, self.embed_tokens.weight, self.embed_positions.weight, ln.weight, ln.bias, self.embed_scale,
                          self.dropout, self.training, self.padding_idx)
@@ -421,10 +470,16 @@ class BartDecoder(nn.Module):
         kv_all = ops.linear(encoder_hidden_states, self.layers[0].encoder_attn.k_proj.weight, self.s_kv_all)     # [B, S, n*2d]
         kvs, bank = ops.split_kv(kv_all, n)
         for i, layer in enumerate(self.layers):
-            h = layer(h, None, enc_mask, kv=kvs[i], bank=bank, slot=i)
+            h = layer(h, None, enc_mask, kv=kvs[i], bank=bank, slot=i, output_attentions=oa)
+            if oa:
+                h, ms, mc = h
+                self_maps.append(ms)
+                cross_maps.append(mc)
             if output_hidden_states:
                 h, keep = ops.fork(h)          # every state has two consumers (next layer / lm_head, and the caller)
                 states.append(keep)
+        if oa:
+            return h, states, tuple(self_maps), tuple(cross_maps)
         return h, states
 
 
@@ -452,7 +507,13 @@ class BartModel(nn.Module):
         return self.decoder
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, image_features=None, face_features=None,
-                face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, encoder_outputs=None, **unused):
+                face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, encoder_outputs=None, output_attentions=None,
+                **unused):
+        """output_attentions (None: config.output_attentions, MFULL:1754) adds `encoder_attentions`, `decoder_attentions`,
+        `cross_attentions` (the reference's fields) and `encoder_name_face_attentions`, `encoder_img_ner_cross_attentions` (the two
+        maps the reference discards) — tuples with one fp32 map per layer, see BartEncoderLayer / BartDecoderLayer.  Precomputed
+        `encoder_outputs` contribute their maps only if they were produced with the flag."""
+        oa = bool(output_attentions if output_attentions is not None else self.config.output_attentions)
         if decoder_input_ids is None:
             if input_ids is None:
                 raise ValueError("If no `decoder_input_ids` or `decoder_inputs_embeds` are passed, `input_ids` cannot be `None`.")
@@ -460,12 +521,19 @@ class BartModel(nn.Module):
         if encoder_outputs is None:
             encoder_outputs = self.encoder(input_ids=input_ids, attention_mask=attention_mask, image_features=image_features,
                                            name_ids=name_ids, name_mask=name_mask, face_features=face_features,
-                                           face_mask=face_mask, add_ner_ffn=add_ner_ffn)
-        h, states = self.decoder(decoder_input_ids, encoder_outputs["last_hidden_state"], attention_mask)
-        return {"last_hidden_state": h, "decoder_hidden_states": tuple(states),
-                "encoder_last_hidden_state": encoder_outputs["last_hidden_state"],
-                "hidden_states_face": encoder_outputs["hidden_states_face"], "hidden_states_ner": encoder_outputs["hidden_states_ner"],
-                "hidden_states_img": encoder_outputs["hidden_states_img"]}
+                                           face_mask=face_mask, add_ner_ffn=add_ner_ffn, output_attentions=oa)
+        h, states, *maps = self.decoder(decoder_input_ids, encoder_outputs["last_hidden_state"], attention_mask, output_attentions=oa)
+        out = {"last_hidden_state": h, "decoder_hidden_states": tuple(states),
+               "encoder_last_hidden_state": encoder_outputs["last_hidden_state"],
+               "hidden_states_face": encoder_outputs["hidden_states_face"], "hidden_states_ner": encoder_outputs["hidden_states_ner"],
+               "hidden_states_img": encoder_outputs["hidden_states_img"]}
+        if oa:
+            out["decoder_attentions"], out["cross_attentions"] = maps
+            for key, src in (("encoder_attentions", "attentions"), ("encoder_name_face_attentions", "name_face_attentions"),
+                             ("encoder_img_ner_cross_attentions", "img_ner_cross_attentions")):
+                if src in encoder_outputs:
+                    out[key] = encoder_outputs[src]
+        return out
 
 
 def init_attn_weight_encoder(encoder):
@@ -568,14 +636,18 @@ class BartForMultiModalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, image_features=None, face_features=None,
                 face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, labels=None, output_logits=None,
-                encoder_outputs=None, **unused):
+                encoder_outputs=None, output_attentions=None, **unused):
+        """output_attentions=True (None: config.output_attentions, MFULL:1944) adds the attention maps to the returned dict —
+        see BartModel.forward.  They are the pre-dropout softmax, fp32, without an autograd graph.  generate() does not return
+        maps."""
         if self.arena is None:
             raise RuntimeError("call model.finalize(device) before forward (parameters must live in the HBM arena)")
         if labels is not None and decoder_input_ids is None:
             _, decoder_input_ids = K.prep_ids(labels, self.config.pad_token_id, self.config.decoder_start_token_id, want_mask=False)
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, decoder_input_ids=decoder_input_ids,
                          image_features=image_features, face_features=face_features, face_mask=face_mask, name_ids=name_ids,
-                         name_mask=name_mask, add_ner_ffn=add_ner_ffn, encoder_outputs=encoder_outputs)
+                         name_mask=name_mask, add_ner_ffn=add_ner_ffn, encoder_outputs=encoder_outputs,
+                         output_attentions=output_attentions)
         h = out.pop("last_hidden_state")
         want_logits = output_logits if output_logits is not None else labels is None
         if labels is not None:
@@ -602,11 +674,12 @@ class BartForMultiModalGeneration(nn.Module):
 
     @torch.no_grad()
     def greedy_generate(self, input_ids, attention_mask, max_length, **kw):
+        kw["output_attentions"] = False             # decoding returns ids only: no maps whatever config.output_attentions says
         enc = self.model.encoder(input_ids=input_ids, attention_mask=attention_mask, **kw)
         B = input_ids.shape[0]
         ids = torch.full((B, 1), self.config.decoder_start_token_id, dtype=torch.long, device=input_ids.device)
         for _ in range(max_length - 1):
-            h, _ = self.model.decoder(ids, enc["last_hidden_state"], attention_mask, output_hidden_states=False)
+            h, _ = self.model.decoder(ids, enc["last_hidden_state"], attention_mask, output_hidden_states=False, output_attentions=False)
             last = h[:, -1].contiguous()
             lg = ops.linear(last, self.model.shared.weight, self.s_lm)
             nxt = K.argmax_rows(lg, self.V)

@@ -209,7 +209,7 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
         kw = dict(face_features=batch["face_emb"], face_mask=K.face_mask(batch["face_emb"]), name_ids=batch["names_art_ids"],
                   name_mask=names_mask)
     out = model(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in, image_features=img_cls, labels=tgt,
-                output_logits=False, add_ner_ffn=True, **kw)                                  # TRAIN:281 + fused CE (TRAIN:287)
+                output_logits=False, add_ner_ffn=True, output_attentions=False, **kw)         # TRAIN:281 + fused CE (TRAIN:287); the step uses no maps
     txt = out["loss"]
     colam = secla = None
     if guide is not None:
