@@ -260,11 +260,16 @@ int vacnic_embed_ln_bwd(const vacnic_embed_ln_bwd_args* a, void* stream);
  * (f32 atomics; caller zeroes them) so that loss = loss_sum / count.
  * vacnic_ce_bwd writes dlogits bf16 [R][ldd] = (softmax - onehot) * valid * grad_scale * (*grad_out) / (*count);
  * columns [V, ldd) are zero-filled.  dlogits may alias bf16 logits when ldd == ldl.
+ * label_smoothing = eps in [0, 1) (anything else: VACNIC_BAD_SHAPE), torch's CrossEntropyLoss(label_smoothing=eps):
+ *   row_loss = (1 - eps) (lse - z_t) + eps (lse - mean_{j < V} z_j),   dlogits = (softmax - (1 - eps) onehot - eps / V) * ...
+ * (kernels of their own; eps == 0, e.g. a zero-initialised struct, launches the plain kernels: same row_lse, count and dlogits bit for
+ * bit, loss_sum up to the order of its atomic additions).
  */
 typedef struct {
   const void* logits; const int64_t* targets; float* row_lse; float* row_loss; float* loss_sum; float* count;
   void* dlogits; const float* grad_out; float grad_scale;
   int64_t R, V, ldl, ldd; int64_t ignore_index; int32_t logits_f32;
+  float label_smoothing;
 } vacnic_ce_args;
 int vacnic_ce_fwd(const vacnic_ce_args* a, void* stream);
 int vacnic_ce_bwd(const vacnic_ce_args* a, void* stream);
@@ -498,16 +503,32 @@ int vacnic_image_u8_normalize(const uint8_t* src, const uint8_t* flip, float* ds
  *   vacnic_lmhead_ce_dlogits  recomputes the logits of vocabulary columns [col0, col0 + ncols) and writes
  *                             dlogits = (softmax - onehot(target)) * rowp[.][1] as bf16 [R][lddl] (columns ncols..round_up(ncols,8)
  *                             are written as zeros); the caller runs the dh / dE GEMMs on the chunk and re-uses the buffer.
+ * Label smoothing (label_smoothing = eps in [0, 1); anything else: VACNIC_BAD_SHAPE), torch's CrossEntropyLoss(label_smoothing=eps)
+ * over the V real columns:  row_loss = (1 - eps) (lse - z_t) + eps (lse - mean_j z_j),
+ *                           dlogits  = (softmax - (1 - eps) onehot(target) - eps / V) * coef.
+ *   eps > 0: vacnic_lmhead_ce_fwd also needs part_sum[R][part_tiles] (the epilogue's per-tile sums of the valid logits), and
+ *            vacnic_lmhead_ce_dlogits reads rowp as FOUR floats per row, 16-byte aligned, written by vacnic_lmhead_ce_rowp_smooth:
+ *            rowp[R][4] = {row_lse, coef, coef * (1 - eps), coef * eps / V}.  row_lse does not depend on eps.
+ *   eps == 0 (a zero-initialised tail of the struct): part_sum is not touched, rowp is the [R][2] array of vacnic_lmhead_ce_rowp, the
+ *            kernels launched are the ones without the option: row_lse, count and dlogits are bit-identical to theirs; loss_sum is,
+ *            as always, an fp32 atomic sum over the rows, equal up to the order of its additions.
  */
 typedef struct {
   const void* h; const void* emb; const float* bias;      /* bf16 [R][ldh], bf16 [>=V][lde] (tied embedding), f32 [V] or NULL */
   const int64_t* targets;                                 /* [R] */
   float* part; float* tl; float* row_lse; float* loss_sum; float* count;
   int64_t R, V, D, ldh, lde, part_tiles, ignore_index;
+  float* part_sum;                                        /* f32 [R][part_tiles] contiguous scratch (R * part_tiles floats, written with
+                                                             4-byte stores: no alignment beyond a float's), label_smoothing > 0 only
+                                                             (else may be NULL and is never read or written) */
+  float label_smoothing;
 } vacnic_lmhead_ce_args;
 int vacnic_lmhead_ce_fwd(const vacnic_lmhead_ce_args* a, void* stream);
 int vacnic_lmhead_ce_rowp(const float* row_lse, const int64_t* targets, const float* count, const float* grad_out,
                           float grad_scale, float* rowp, int64_t R, int64_t ignore_index, void* stream);
+int vacnic_lmhead_ce_rowp_smooth(const float* row_lse, const int64_t* targets, const float* count, const float* grad_out,
+                                 float grad_scale, float label_smoothing, int64_t V, float* rowp, int64_t R, int64_t ignore_index,
+                                 void* stream);
 int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t col0, int64_t ncols, void* dl, int64_t lddl,
                              const float* rowp, void* stream);
 

@@ -23,6 +23,7 @@ parser = _full.parser
 parser.add_argument("--do_retrieval", action="store_true")        # TRAINV: retrieved-sentence articles; a data-side switch
 parser.set_defaults(only_image=True, no_mapping=True, use_secla=False, plm_type="facebook/bart-base", clip_type="ViT-B/16")
 run = _full.run
+build_config = _full.build_config
 
 
 if __name__ == "__main__":

@@ -81,6 +81,9 @@ parser.add_argument("--launch_plan", default=True, type=_b, help="record the ste
 parser.add_argument("--resume", type=str, default="", help="checkpoint written by a previous run (<out_dir>/<experiment_name>last.pt): "
                     "weights, AdamW moments, LR-schedule position and dropout RNG are restored and the step count continues")
 
+parser.add_argument("--label_smoothing", type=float, default=0.0, help="label smoothing of the training text loss, as torch's "
+                    "CrossEntropyLoss(label_smoothing=) (0.1 in the usual BART fine-tuning recipe); the validation loss stays the plain NLL")
+
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
        "facebook/bart-large": dict(), "patrickvonplaten/bart-large-fp32": dict()}
@@ -90,11 +93,22 @@ CLIP = {"ViT-B/32": dict(width=768, layers=12, patch_size=32, output_dim=512), "
         "ViT-L/14": dict(width=1024, layers=24, patch_size=14, output_dim=768)}
 
 
+def build_config(args):
+    """(VacnicConfig, ClipVisionConfig) for the parsed flags; the config is what a checkpoint's meta.config records."""
+    from vacnic_amd.config import HUB_MODEL_DROPOUTS, ClipVisionConfig, VacnicConfig
+    vkw = CLIP[args.clip_type]
+    cfg = VacnicConfig(enc_fusion_layer=list(args.enc_fusion_layer or []), dim_common=args.dim_common, prompt_size=args.prompt_size,
+                       max_ner_type_len=args.max_ner_type_len, max_ner_type_len_gt=args.max_ner_type_len_gt,
+                       only_image=args.only_image, clip_width=vkw["width"], prompt_mlp_type=args.prompt_mlp_type, map_size=args.map_size,
+                       init_attn_weight=args.init_attn_weight, label_smoothing=getattr(args, "label_smoothing", 0.0),
+                       **PLM[args.plm_type], **HUB_MODEL_DROPOUTS[args.plm_type]).validate()
+    return cfg, ClipVisionConfig(**vkw)
+
+
 def run(args, batches=None):
     import torch
     import torch.distributed as dist
     from vacnic_amd import ops, streams, synthetic
-    from vacnic_amd.config import HUB_MODEL_DROPOUTS, ClipVisionConfig, VacnicConfig
     from vacnic_amd.ddp import DistributedDataParallel
     from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, TrainArgs, build_models, eval_epoch, gen_caption_from_loader_bart, to_device,
                                      train_step)
@@ -114,13 +128,7 @@ def run(args, batches=None):
         dist.init_process_group(backend=be, **({"device_id": torch.device("cuda", local)} if be == "nccl" else {}))
     ops.Rng.manual_seed(int(args.seed) + rank)
     streams.enable(True)                     # guide forward + weight gradients on side streams
-    vkw = CLIP[args.clip_type]
-    cfg = VacnicConfig(enc_fusion_layer=list(args.enc_fusion_layer or []), dim_common=args.dim_common, prompt_size=args.prompt_size,
-                       max_ner_type_len=args.max_ner_type_len, max_ner_type_len_gt=args.max_ner_type_len_gt,
-                       only_image=args.only_image, clip_width=vkw["width"], prompt_mlp_type=args.prompt_mlp_type, map_size=args.map_size,
-                       init_attn_weight=args.init_attn_weight,
-                       **PLM[args.plm_type], **HUB_MODEL_DROPOUTS[args.plm_type]).validate()
-    vcfg = ClipVisionConfig(**vkw)
+    cfg, vcfg = build_config(args)
     model, guide, _ = build_models(cfg, vcfg, device="cuda", seed=int(args.seed) % (2 ** 31), init="device")
     # Steps per epoch: the reference derives num_training_steps from the dataset (num_epoch * train_size / batch, TRAIN:99); with
     # a real shard an epoch is len(loader) steps, and that value — not the synthetic driver's --steps_per_epoch — must size the

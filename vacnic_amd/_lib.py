@@ -94,7 +94,8 @@ EmbedLnBwdArgs = _struct("vacnic_embed_ln_bwd_args", [
 CeArgs = _struct("vacnic_ce_args", [
     ("logits", vp), ("targets", vp), ("row_lse", vp), ("row_loss", vp), ("loss_sum", vp), ("count", vp),
     ("dlogits", vp), ("grad_out", vp), ("grad_scale", f32),
-    ("R", i64), ("V", i64), ("ldl", i64), ("ldd", i64), ("ignore_index", i64), ("logits_f32", i32)])
+    ("R", i64), ("V", i64), ("ldl", i64), ("ldd", i64), ("ignore_index", i64), ("logits_f32", i32),
+    ("label_smoothing", f32)])
 
 ColamFwdArgs = _struct("vacnic_colam_fwd_args", [
     ("hs", vp), ("hg", vp), ("mask", vp), ("loss", vp), ("cos", vp), ("pooled_s", vp), ("pooled_g", vp),
@@ -119,7 +120,8 @@ NameEmbedArgs = _struct("vacnic_name_embed_args", [
 
 LmheadCeArgs = _struct("vacnic_lmhead_ce_args", [
     ("h", vp), ("emb", vp), ("bias", vp), ("targets", vp), ("part", vp), ("tl", vp), ("row_lse", vp), ("loss_sum", vp), ("count", vp),
-    ("R", i64), ("V", i64), ("D", i64), ("ldh", i64), ("lde", i64), ("part_tiles", i64), ("ignore_index", i64)])
+    ("R", i64), ("V", i64), ("D", i64), ("ldh", i64), ("lde", i64), ("part_tiles", i64), ("ignore_index", i64),
+    ("part_sum", vp), ("label_smoothing", f32)])
 
 BeamState = _struct("vacnic_beam_state", [
     ("seq0", vp), ("seq1", vp), ("beam_scores", vp), ("done", vp), ("hyp_cnt", vp), ("hyp_worst", vp), ("hyp_score", vp), ("hyp_len", vp),
@@ -184,6 +186,7 @@ _PLAIN_FNS = {
     "vacnic_gather_rows": [vp, vp, vp, i64, i64, i64, i64, vp],
     "vacnic_image_u8_normalize": [vp, vp, vp, i64, i64, i64, f32, f32, f32, f32, f32, f32, vp],
     "vacnic_lmhead_ce_rowp": [vp, vp, vp, vp, f32, vp, i64, i64, vp],
+    "vacnic_lmhead_ce_rowp_smooth": [vp, vp, vp, vp, f32, f32, i64, vp, i64, i64, vp],
     "vacnic_lmhead_ce_dlogits": [C.POINTER(LmheadCeArgs), i64, i64, vp, i64, vp, vp],
     "vacnic_zero_bytes": [vp, i64, vp],
     "vacnic_beam_init": [C.POINTER(BeamState), i32, vp],

@@ -39,6 +39,7 @@ class VacnicConfig:
     face_dim: int = 512
     clip_width: int = 768              # input dim of the ClipCap MLP (hard-coded 768 at MFULL:1136; 1024 for ViT-L/14)
     output_attentions: bool = False    # BartConfig.output_attentions: default of forward(output_attentions=None) (MFULL:1225,1533,1754)
+    label_smoothing: float = 0.0       # training loss: CrossEntropyLoss(label_smoothing=) in forward(labels=...); validation stays the plain NLL
 
     @property
     def head_dim(self):
@@ -50,6 +51,8 @@ class VacnicConfig:
         return self.prompt_size if self.prompt_mlp_type == "clipcap" else int(self.map_size[-1])
 
     def validate(self):
+        if not 0.0 <= float(self.label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {self.label_smoothing!r}")
         if self.d_model not in (768, 1024):
             raise ValueError("d_model must be 768 or 1024 (prompt is reshaped to [B,P,768], MFULL:1143-1144,1275-1278)")
         if self.d_model % self.encoder_attention_heads or self.d_model // self.encoder_attention_heads != 64:

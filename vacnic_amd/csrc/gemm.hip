@@ -295,7 +295,7 @@ static double cfg_cost(const TileCfg& c, int64_t M, int64_t N, int64_t kper, int
   return (double)rounds * ((double)c.per_cu * c.bm * c.bn * (double)kper / c.eff + kFixedUnits);
 }
 
-static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0);
+static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0, bool ce_smooth = false);
 
 // fix-up buffers: partial tiles are padded to whole tiles; the bound covers every configuration (64-row tiles pad M the least,
 // 256 x 256 the most), so the caller need not know which one a launch picks
@@ -354,7 +354,7 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
   return gemm_one(&tail_a, kCfgs[2].hint, stream);
 }
 
-static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0) {
+static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0, bool ce_smooth) {
   VCHECK((a->ldx & 7) == 0 && (a->ldw & 7) == 0, VACNIC_MISALIGNED, "gemm: ldx/ldw must be multiples of 8");
   VCHECK(aligned16(a->x) && aligned16(a->w), VACNIC_MISALIGNED, "gemm: x/w must be 16-byte aligned");
   VCHECK(a->out_mode >= 0 && a->out_mode <= 2, VACNIC_BAD_DTYPE, "gemm: bad out_mode %d", a->out_mode);
@@ -448,6 +448,7 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
   if (force == 261) return launch_t261(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (force == 262) return launch_t262(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (force == 264) return launch_t264(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong, half-width tile
+  if (ce_mode && ce_smooth) return launch_t256cels(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // label smoothing: its own kernel
   if (ce_mode) return launch_t256ce(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (big) return launch_t256(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong loop
   if (mid) return launch_t128(p, a->x_kstrided, a->w_kstrided, zsplits, s);
@@ -515,6 +516,10 @@ extern "C" int vacnic_wgrad_group(const vacnic_wgrad_job* jobs, int64_t njobs, v
 // [R, V] logits are never written.  Forward = one GEMM whose epilogue reduces every 256-column tile of a row to an
 // online-softmax pair and picks the target's logit, plus a small combine; backward recomputes the logits one vocabulary
 // chunk at a time straight into bf16 dlogits (vacnic_lmhead_ce_dlogits), which the caller feeds to the dh / dE GEMMs.
+// Label smoothing (label_smoothing = eps > 0, torch's CrossEntropyLoss(label_smoothing=)): row_loss = (1 - eps) (lse - z_t) +
+// eps (lse - mean_j z_j) and dz_j = (softmax_j - (1 - eps) [j == t] - eps / V) g / count.  The forward epilogue also keeps the sum
+// of each tile's valid logits (part_sum), the backward reads four floats per row; both are kernels of their own
+// (gemm_t256cels.hip, ce_smooth_term_kernel, ce_rowp_smooth_kernel), so eps == 0 launches exactly what it always did.
 namespace {
 __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict__ part, const float* __restrict__ tl,
                                                           const int64_t* __restrict__ targets, float* __restrict__ row_lse,
@@ -550,6 +555,39 @@ __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict
   }
 }
 
+// label smoothing: (1 - eps) (lse - z_t) + eps (lse - mean_j z_j) = (lse - z_t) + eps (z_t - mean_j z_j).  ce_combine_kernel has added the
+// first term; this adds the second from the per-tile logit sums (mean over the V real columns), so row_lse is the plain path's.
+__global__ __launch_bounds__(256) void ce_smooth_term_kernel(const float* __restrict__ part_sum, const float* __restrict__ tl,
+                                                              const int64_t* __restrict__ targets, float* __restrict__ loss_sum,
+                                                              int R, int tiles, int64_t ignore, float eps, float inv_v) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.x * 4 + wave;
+  float term = 0.f;
+  if (r < R && targets[r] != ignore) {             // (wave-uniform)
+    float zs = 0.f;
+    for (int t = lane; t < tiles; t += 64) zs += part_sum[(size_t)r * tiles + t];
+    term = eps * (tl[r] - wave_sum(zs) * inv_v);
+  }
+  __shared__ float red[4];
+  if (lane == 0) red[wave] = term;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float t4 = red[0] + red[1] + red[2] + red[3];
+    if (t4 != 0.f) atomicAdd(loss_sum, t4);
+  }
+}
+
+// rowp[R][4] = {lse, g, g (1 - eps), g eps / V}: what the label-smoothing dlogits epilogue reads per row (one 16-byte load)
+__global__ void ce_rowp_smooth_kernel(const float* __restrict__ row_lse, const int64_t* __restrict__ targets, const float* __restrict__ count,
+                                      const float* __restrict__ grad_out, float grad_scale, float eps, float inv_v,
+                                      float* __restrict__ rowp, int R, int64_t ignore) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float c = fmaxf(*count, 1.f);
+  const float g = targets[r] != ignore ? (grad_out ? *grad_out : 1.f) * grad_scale / c : 0.f;
+  *(f32x4*)(rowp + 4 * (size_t)r) = (f32x4){row_lse[r], g, g * (1.f - eps), g * eps * inv_v};
+}
+
 __global__ void ce_rowp_kernel(const float* __restrict__ row_lse, const int64_t* __restrict__ targets, const float* __restrict__ count,
                                const float* __restrict__ grad_out, float grad_scale, float* __restrict__ rowp, int R, int64_t ignore) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -574,6 +612,9 @@ extern "C" int vacnic_lmhead_ce_fwd(const vacnic_lmhead_ce_args* a, void* stream
   VCHECK(a && a->h && a->emb && a->targets && a->part && a->tl && a->row_lse && a->loss_sum && a->count, VACNIC_BAD_SHAPE,
          "lmhead_ce_fwd: null operand");
   VCHECK(a->R > 0 && a->V > 0 && a->D > 0, VACNIC_BAD_SHAPE, "lmhead_ce_fwd: empty problem");
+  VCHECK(a->label_smoothing >= 0.f && a->label_smoothing < 1.f, VACNIC_BAD_SHAPE, "lmhead_ce_fwd: label_smoothing %g outside [0, 1)", (double)a->label_smoothing);
+  const bool smooth = a->label_smoothing > 0.f;
+  VCHECK(!smooth || a->part_sum, VACNIC_BAD_SHAPE, "lmhead_ce_fwd: label_smoothing > 0 needs the part_sum scratch [R][part_tiles]");
   const int64_t tiles = (a->V + 255) / 256;
   VCHECK(a->part_tiles >= tiles, VACNIC_BAD_SHAPE, "lmhead_ce_fwd: part holds %ld tiles per row, %ld needed", (long)a->part_tiles, (long)tiles);
   hipStream_t st = (hipStream_t)stream;
@@ -589,6 +630,17 @@ extern "C" int vacnic_lmhead_ce_fwd(const vacnic_lmhead_ce_args* a, void* stream
   if (a->part_tiles != tiles) {          // the kernel indexes part[m][tiles_n] with ITS tile count
     vacnic_set_error("lmhead_ce_fwd: part_tiles must equal ceil(V / 256) = %ld", (long)tiles);
     return VACNIC_BAD_SHAPE;
+  }
+  if (smooth) {
+    g.out = a->part_sum;                 // the label-smoothing epilogue writes the per-tile logit sums through `out`
+    if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0, true)) return e;
+    hipLaunchKernelGGL(ce_combine_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part, a->tl, a->targets, a->row_lse,
+                       a->loss_sum, a->count, (int)a->R, (int)tiles, a->ignore_index);
+    VLAUNCH_CHECK();
+    hipLaunchKernelGGL(ce_smooth_term_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part_sum, a->tl, a->targets,
+                       a->loss_sum, (int)a->R, (int)tiles, a->ignore_index, a->label_smoothing, 1.f / (float)a->V);
+    VLAUNCH_CHECK();
+    return VACNIC_OK;
   }
   if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0)) return e;
   hipLaunchKernelGGL(ce_combine_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part, a->tl, a->targets, a->row_lse,
@@ -607,10 +659,26 @@ extern "C" int vacnic_lmhead_ce_rowp(const float* row_lse, const int64_t* target
   return VACNIC_OK;
 }
 
+extern "C" int vacnic_lmhead_ce_rowp_smooth(const float* row_lse, const int64_t* targets, const float* count, const float* grad_out,
+                                            float grad_scale, float label_smoothing, int64_t V, float* rowp, int64_t R,
+                                            int64_t ignore_index, void* stream) {
+  VPLAN_REC(vacnic_lmhead_ce_rowp_smooth, row_lse, targets, count, grad_out, grad_scale, label_smoothing, V, rowp, R, ignore_index, stream);
+  VCHECK(row_lse && targets && count && rowp && R > 0 && V > 0, VACNIC_BAD_SHAPE, "lmhead_ce_rowp_smooth: bad operand");
+  VCHECK(label_smoothing >= 0.f && label_smoothing < 1.f, VACNIC_BAD_SHAPE, "lmhead_ce_rowp_smooth: label_smoothing %g outside [0, 1)", (double)label_smoothing);
+  VCHECK(aligned16(rowp), VACNIC_MISALIGNED, "lmhead_ce_rowp_smooth: rowp must be 16-byte aligned");
+  hipLaunchKernelGGL(ce_rowp_smooth_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, row_lse, targets, count,
+                     grad_out, grad_scale, label_smoothing, 1.f / (float)V, rowp, (int)R, ignore_index);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
 extern "C" int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t col0, int64_t ncols, void* dl, int64_t lddl,
                                         const float* rowp, void* stream) {
   VPLAN_REC_STRUCT(vacnic_lmhead_ce_dlogits, a, col0, ncols, dl, lddl, rowp, stream);
   VCHECK(a && a->h && a->emb && a->targets && dl && rowp, VACNIC_BAD_SHAPE, "lmhead_ce_dlogits: null operand");
+  VCHECK(a->label_smoothing >= 0.f && a->label_smoothing < 1.f, VACNIC_BAD_SHAPE, "lmhead_ce_dlogits: label_smoothing %g outside [0, 1)", (double)a->label_smoothing);
+  const bool smooth = a->label_smoothing > 0.f;        // rowp then holds 4 floats per row (vacnic_lmhead_ce_rowp_smooth)
+  VCHECK(!smooth || aligned16(rowp), VACNIC_MISALIGNED, "lmhead_ce_dlogits: the 4-float rowp of label smoothing must be 16-byte aligned");
   VCHECK(col0 >= 0 && ncols > 0 && col0 + ncols <= a->V, VACNIC_BAD_SHAPE, "lmhead_ce_dlogits: chunk [%ld, +%ld) outside V=%ld",
          (long)col0, (long)ncols, (long)a->V);
   VCHECK((lddl & 7) == 0 && lddl >= ((ncols + 7) & ~7LL) && aligned16(dl), VACNIC_MISALIGNED, "lmhead_ce_dlogits: dl rows must be 16-byte aligned and hold round_up(ncols, 8)");
@@ -619,5 +687,5 @@ extern "C" int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t 
   if (g.bias) g.bias = a->bias + col0;
   g.out = dl; g.ldo = lddl;
   g.dact_src = a->targets; g.residual = rowp;
-  return gemm_one(&g, 256 + 64000, stream, 4, (int)col0);
+  return gemm_one(&g, 256 + 64000, stream, 4, (int)col0, smooth);
 }

@@ -252,9 +252,12 @@ __device__ __forceinline__ void wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%
 // scratch.  A DR kernel always applies dropout (the host launches it only with drop_thr != 0).
 // CE: compile the fused LM-head cross-entropy epilogues (out_mode 3 / 4) — their own instantiation (gemm_t256ce.hip): inside the
 // general kernels their code raised the register allocation of EVERY epilogue path (128x128 tiles: 181 -> 256 VGPRs + scratch).
+// LS (with CE): the label-smoothing variants of the two cross-entropy epilogues (gemm_t256cels.hip) — again their own instantiation, so
+// that the CE kernels a run without smoothing launches stay exactly as they are.  Forward: additionally the sum of the tile's valid
+// logits -> part_sum[m][tn] (p.out).  Backward: p.residual holds FOUR floats per row {lse, coef, coef * (1 - eps), coef * eps / V}.
 // One output tile: rows [m0, m0 + BM) x columns [n0, n0 + BN), reduction slice `zsplit`.  `tn` = this tile's column index inside
 // its row panel and p.tiles_n the number of tiles that share the panel (the xsum K-steps are dealt round-robin over them).
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false>
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false, bool LS = false>
 __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const int n0, const int tn, const int zsplit, const int tile_id = 0) {
   constexpr int NWAVE = WM * WN, NTHR = 64 * NWAVE;
   constexpr int TM = BM / WM, TN = BN / WN;             // per-wave output sub-tile
@@ -751,6 +754,20 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
       const long long tgt = mok ? ((const long long*)p.dact_src)[m] - p.ce_col0 : -1;      // column inside this launch's N range
       if (p.out_mode == 3) {
         float mx = -INFINITY, sm = 0.f;
+        [[maybe_unused]] float zs = 0.f;                      // LS: sum of the valid logits (the uniform term's mean_j z_j)
+        if constexpr (LS) {
+          // a pass of its own over the staged row: inside the online-softmax loop below the extra add changed how that loop was
+          // compiled (1-ulp differences in `sm`, i.e. a row_lse that depended on the option)
+#pragma unroll
+          for (int j0 = 0; j0 < CPT; j0 += 4) {
+            const f32x4 v4 = *(const f32x4*)(src + j0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int n = nb + j0 + j;
+              if (n < p.N) zs += p.bias ? v4[j] * p.alpha + p.bias[n] : v4[j] * p.alpha;
+            }
+          }
+        }
 #pragma unroll
         for (int j0 = 0; j0 < CPT; j0 += 4) {
           const f32x4 v4 = *(const f32x4*)(src + j0);
@@ -773,13 +790,22 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
           const float nm = fmaxf(mx, omx);
           sm = (mx == -INFINITY ? 0.f : sm * __expf(mx - nm)) + (omx == -INFINITY ? 0.f : osm * __expf(omx - nm));
           mx = nm;
+          if constexpr (LS) zs += __shfl_xor(zs, o, 64);
         }
         if (seg == 0 && mok) {
           float* part = (float*)p.preact + ((size_t)m * p.tiles_n + tn) * 2;
           part[0] = mx; part[1] = sm;
+          if constexpr (LS) ((float*)p.out)[(size_t)m * p.tiles_n + tn] = zs;
         }
       } else if (mok) {
-        const float lse = ((const float*)p.residual)[2 * m], coef = ((const float*)p.residual)[2 * m + 1];
+        float lse, coef;
+        [[maybe_unused]] float c_hot = 0.f, c_uni = 0.f;      // LS: coef * (1 - eps) on the target column, coef * eps / V on every column
+        if constexpr (LS) {
+          const f32x4 rp = ((const f32x4*)p.residual)[m];
+          lse = rp[0]; coef = rp[1]; c_hot = rp[2]; c_uni = rp[3];
+        } else {
+          lse = ((const float*)p.residual)[2 * m]; coef = ((const float*)p.residual)[2 * m + 1];
+        }
         bf16_t* orow = (bf16_t*)p.out + (size_t)m * p.ldo;
 #pragma unroll
         for (int j0 = 0; j0 < CPT; j0 += 8) {
@@ -791,7 +817,8 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
           for (int j = 0; j < 8; ++j) {
             float v = (j < 4 ? a4[j & 3] : b4[j & 3]) * p.alpha;
             if (p.bias && n + j < p.N) v += p.bias[n + j];
-            d[j] = n + j < p.N ? (__expf(v - lse) - (n + j == tgt ? 1.f : 0.f)) * coef : 0.f;     // pad columns: exact zeros
+            if constexpr (LS) d[j] = n + j < p.N ? __expf(v - lse) * coef - (n + j == tgt ? c_hot : 0.f) - c_uni : 0.f;
+            else d[j] = n + j < p.N ? (__expf(v - lse) - (n + j == tgt ? 1.f : 0.f)) * coef : 0.f;     // pad columns: exact zeros
           }
           store8bf(orow + n, d);                            // ldo % 8 == 0 and 16-byte rows are checked on the host
         }
@@ -920,6 +947,34 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
   gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XKS, WKS, CE, DR>(p, tm * BM, tn * BN, tn, zsplit, bid);
 }
 
+// The cross-entropy kernel with the label-smoothing epilogues (forward layout, no split-K): the same tile walk as gemm_kernel.
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+__global__ __launch_bounds__(64 * WM * WN, 2) void gemm_ce_smooth_kernel(GemmP p) {
+  if (p.debug & 8) return;
+  const int nt = p.tiles_m * p.tiles_n;
+  const int q = nt >> 3, r = nt & 7, xcd = blockIdx.x & 7;
+  const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
+  const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
+  gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, false, false, true, false, true>(p, tm * BM, tn * BN, tn, 0, bid);
+}
+
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+int launch_gemm_ce_smooth(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
+  if (xks || wks || zsplits != 1) { vacnic_set_error("gemm: the cross-entropy epilogues are built for the forward layout without split-K"); return VACNIC_UNSUPPORTED; }
+  GemmP p = p0;
+  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
+  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
+  static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
+  auto kern = gemm_ce_smooth_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>;
+  if (lds > 65536) {
+    static bool once = false;
+    if (!once) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; }
+  }
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds, s, p);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Grouped weight gradients: several independent dW[N,K] += dY[M,N]^T X[M,K] problems in ONE launch, no split-K.
 // A UNIT is a block of up to UT x UT output tiles of one problem with the FULL reduction; unit u runs on XCD u % 8 (workgroup L
@@ -1025,6 +1080,7 @@ int launch_t260(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t261(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t262(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t256ce(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s); // 256x256 ping-pong + LM-head cross-entropy epilogues
+int launch_t256cels(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s); // ... with the label-smoothing variants of those epilogues (LS)
 int launch_t256d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);  // the same tiles with the activation-dropout epilogues (DR)
 int launch_t264d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t64d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);

@@ -35,12 +35,16 @@ __device__ __forceinline__ float ld_logit(const void* row, int j) {
 }
 
 // ---- cross entropy --------------------------------------------------------------------------
-template <bool F32>
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
-                                                     float* __restrict__ row_lse, float* __restrict__ row_loss,
-                                                     float* __restrict__ loss_sum, float* __restrict__ count,
-                                                     int V, long ldl, int64_t ignore_index) {
+// LS: label smoothing (torch's CrossEntropyLoss(label_smoothing=eps)): row_loss = (1 - eps) (lse - z_t) + eps (lse - mean_j z_j), so the
+// pass also sums the logits.  The smoothing kernels are separate __global__ functions around the same body: eps == 0 launches the
+// kernels it always did.
+template <bool F32, bool LS>
+__device__ __forceinline__ void ce_fwd_body(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                            float* __restrict__ row_lse, float* __restrict__ row_loss,
+                                            float* __restrict__ loss_sum, float* __restrict__ count,
+                                            int V, long ldl, int64_t ignore_index, float eps) {
   __shared__ float red[8];
+  [[maybe_unused]] float zs = 0.f;               // LS: this thread's share of sum_j z_j
   const long r = blockIdx.x;
   const char* row = (const char*)logits + r * ldl * (F32 ? 4 : 2);
   // online max/sum: each thread keeps (m, s)
@@ -59,11 +63,16 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
       float cs = 0.f;
 #pragma unroll
       for (int i = 0; i < 8; ++i) cs += __expf(v[i] - nm);
+      if constexpr (LS) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) zs += v[i];
+      }
       s = s * __expf(m - nm) + cs;
       m = nm;
     }
     for (int j = (nchunk << 3) + threadIdx.x; j < V; j += 256) {
       const float v = ld_logit<F32>(row, j);
+      if constexpr (LS) zs += v;
       const float nm = fmaxf(m, v);
       s = s * __expf(m - nm) + __expf(v - nm);
       m = nm;
@@ -81,11 +90,16 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
       float cs = 0.f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) cs += __expf(a[i] - nm) + __expf(b[i] - nm);      // exp(-inf) = 0 for the absent vector
+      if constexpr (LS) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zs += a[i] + (two ? b[i] : 0.f);
+      }
       s = s * __expf(m - nm) + cs;
       m = nm;
     }
     for (int j = (nvec << 2) + threadIdx.x; j < V; j += 256) {
       const float v = ld_logit<F32>(row, j);
+      if constexpr (LS) zs += v;
       const float nm = fmaxf(m, v);
       s = s * __expf(m - nm) + __expf(v - nm);
       m = nm;
@@ -93,6 +107,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
   }
   const float gm = block_max(m, red);
   const float gs = block_sum(m == -INFINITY ? 0.f : s * __expf(m - gm), red);
+  [[maybe_unused]] float zmean = 0.f;
+  if constexpr (LS) zmean = block_sum(zs, red) / (float)V;
   if (threadIdx.x == 0) {
     const float lse = gm + __logf(gs);
     row_lse[r] = lse;
@@ -100,6 +116,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
     float l = 0.f;
     if (t != ignore_index && t >= 0 && t < V) {
       l = lse - ld_logit<F32>(row, (int)t);
+      if constexpr (LS) l = (1.f - eps) * l + eps * (lse - zmean);
       atomicAdd(loss_sum, l);
       atomicAdd(count, 1.f);
     }
@@ -107,13 +124,29 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ lo
   }
 }
 
-// dlogits = (softmax - onehot) * valid * gscale, gscale = grad_scale * (*grad_out) / (*count)
 template <bool F32>
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
-                                                     const float* __restrict__ row_lse, const float* __restrict__ count,
-                                                     const float* __restrict__ grad_out, float grad_scale,
-                                                     bf16_t* __restrict__ dlogits, int V, long ldl, long ldd,
-                                                     int64_t ignore_index) {
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                     float* __restrict__ row_lse, float* __restrict__ row_loss,
+                                                     float* __restrict__ loss_sum, float* __restrict__ count,
+                                                     int V, long ldl, int64_t ignore_index) {
+  ce_fwd_body<F32, false>(logits, targets, row_lse, row_loss, loss_sum, count, V, ldl, ignore_index, 0.f);
+}
+template <bool F32>
+__global__ __launch_bounds__(256) void ce_fwd_smooth_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                            float* __restrict__ row_lse, float* __restrict__ row_loss,
+                                                            float* __restrict__ loss_sum, float* __restrict__ count,
+                                                            int V, long ldl, int64_t ignore_index, float eps) {
+  ce_fwd_body<F32, true>(logits, targets, row_lse, row_loss, loss_sum, count, V, ldl, ignore_index, eps);
+}
+
+// dlogits = (softmax - onehot) * valid * gscale, gscale = grad_scale * (*grad_out) / (*count)
+// LS: dlogits = (softmax - (1 - eps) onehot - eps / V) * valid * gscale
+template <bool F32, bool LS>
+__device__ __forceinline__ void ce_bwd_body(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                            const float* __restrict__ row_lse, const float* __restrict__ count,
+                                            const float* __restrict__ grad_out, float grad_scale,
+                                            bf16_t* __restrict__ dlogits, int V, long ldl, long ldd,
+                                            int64_t ignore_index, float eps) {
   const long r = blockIdx.x;
   const char* row = (const char*)logits + r * ldl * (F32 ? 4 : 2);
   bf16_t* drow = dlogits + r * ldd;
@@ -125,11 +158,32 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const void* __restrict__ lo
     float d = 0.f;
     if (j < V && valid) {
       d = __expf(ld_logit<F32>(row, j) - lse);
-      if (j == (int)t) d -= 1.f;
+      if constexpr (LS) {
+        d -= eps / (float)V;
+        if (j == (int)t) d -= 1.f - eps;
+      } else {
+        if (j == (int)t) d -= 1.f;
+      }
       d *= g;
     }
     drow[j] = f2bf(d);
   }
+}
+template <bool F32>
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                     const float* __restrict__ row_lse, const float* __restrict__ count,
+                                                     const float* __restrict__ grad_out, float grad_scale,
+                                                     bf16_t* __restrict__ dlogits, int V, long ldl, long ldd,
+                                                     int64_t ignore_index) {
+  ce_bwd_body<F32, false>(logits, targets, row_lse, count, grad_out, grad_scale, dlogits, V, ldl, ldd, ignore_index, 0.f);
+}
+template <bool F32>
+__global__ __launch_bounds__(256) void ce_bwd_smooth_kernel(const void* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                            const float* __restrict__ row_lse, const float* __restrict__ count,
+                                                            const float* __restrict__ grad_out, float grad_scale,
+                                                            bf16_t* __restrict__ dlogits, int V, long ldl, long ldd,
+                                                            int64_t ignore_index, float eps) {
+  ce_bwd_body<F32, true>(logits, targets, row_lse, count, grad_out, grad_scale, dlogits, V, ldl, ldd, ignore_index, eps);
 }
 
 // total = ce_sum/count + w_secla*secla + w_colam*colam ; out = {total, txt, secla, colam}
@@ -398,9 +452,20 @@ extern "C" int vacnic_ce_fwd(const vacnic_ce_args* a, void* stream) {
   VPLAN_REC_STRUCT(vacnic_ce_fwd, a, stream);
   VCHECK(a && a->logits && a->targets && a->row_lse && a->loss_sum && a->count, VACNIC_BAD_SHAPE, "ce_fwd: null operand");
   VCHECK(a->V > 0 && a->ldl >= a->V, VACNIC_BAD_SHAPE, "ce_fwd: bad V/ldl");
+  VCHECK(a->label_smoothing >= 0.f && a->label_smoothing < 1.f, VACNIC_BAD_SHAPE, "ce_fwd: label_smoothing %g outside [0, 1)", (double)a->label_smoothing);
   if (a->R == 0) return VACNIC_OK;
   VCHECK(a->logits_f32 || ((a->ldl & 7) == 0 && aligned16(a->logits)), VACNIC_MISALIGNED, "ce_fwd: bf16 logits rows must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
+  if (a->label_smoothing > 0.f) {
+    if (a->logits_f32)
+      hipLaunchKernelGGL(ce_fwd_smooth_kernel<true>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
+                         a->row_loss, a->loss_sum, a->count, (int)a->V, (long)a->ldl, a->ignore_index, a->label_smoothing);
+    else
+      hipLaunchKernelGGL(ce_fwd_smooth_kernel<false>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
+                         a->row_loss, a->loss_sum, a->count, (int)a->V, (long)a->ldl, a->ignore_index, a->label_smoothing);
+    VLAUNCH_CHECK();
+    return VACNIC_OK;
+  }
   if (a->logits_f32)
     hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
                        a->row_loss, a->loss_sum, a->count, (int)a->V, (long)a->ldl, a->ignore_index);
@@ -415,8 +480,21 @@ extern "C" int vacnic_ce_bwd(const vacnic_ce_args* a, void* stream) {
   VPLAN_REC_STRUCT(vacnic_ce_bwd, a, stream);
   VCHECK(a && a->logits && a->targets && a->row_lse && a->count && a->dlogits, VACNIC_BAD_SHAPE, "ce_bwd: null operand");
   VCHECK(a->V > 0 && a->ldl >= a->V && a->ldd >= a->V, VACNIC_BAD_SHAPE, "ce_bwd: bad V/ldl/ldd");
+  VCHECK(a->label_smoothing >= 0.f && a->label_smoothing < 1.f, VACNIC_BAD_SHAPE, "ce_bwd: label_smoothing %g outside [0, 1)", (double)a->label_smoothing);
   if (a->R == 0) return VACNIC_OK;
   hipStream_t s = (hipStream_t)stream;
+  if (a->label_smoothing > 0.f) {
+    if (a->logits_f32)
+      hipLaunchKernelGGL(ce_bwd_smooth_kernel<true>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
+                         a->count, a->grad_out, a->grad_scale, (bf16_t*)a->dlogits, (int)a->V, (long)a->ldl, (long)a->ldd,
+                         a->ignore_index, a->label_smoothing);
+    else
+      hipLaunchKernelGGL(ce_bwd_smooth_kernel<false>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
+                         a->count, a->grad_out, a->grad_scale, (bf16_t*)a->dlogits, (int)a->V, (long)a->ldl, (long)a->ldd,
+                         a->ignore_index, a->label_smoothing);
+    VLAUNCH_CHECK();
+    return VACNIC_OK;
+  }
   if (a->logits_f32)
     hipLaunchKernelGGL(ce_bwd_kernel<true>, dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->targets, a->row_lse,
                        a->count, a->grad_out, a->grad_scale, (bf16_t*)a->dlogits, (int)a->V, (long)a->ldl, (long)a->ldd,

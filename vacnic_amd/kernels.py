@@ -394,7 +394,8 @@ def name_embed_mean(ids3d, embed16, pos16, gamma, beta, embed_scale=1.0, pos_off
 
 
 # ------------------------------------------------------------------------------------------------ losses
-def ce_fwd(logits, targets, V, ignore_index=1):
+def ce_fwd(logits, targets, V, ignore_index=1, label_smoothing=0.0):
+    """label_smoothing: torch's CrossEntropyLoss(label_smoothing=) over the V real columns; 0.0 launches the plain kernels."""
     R, ldl = logits.shape[0], logits.stride(0)
     dev = logits.device
     row_lse = torch.empty(R, device=dev, dtype=torch.float32)
@@ -402,16 +403,16 @@ def ce_fwd(logits, targets, V, ignore_index=1):
     call_struct("vacnic_ce_fwd", stream=_stream(), logits=_p(logits), targets=_p(targets), row_lse=_p(row_lse),
                 row_loss=None, loss_sum=acc.data_ptr(), count=acc.data_ptr() + 4, dlogits=None, grad_out=None,
                 grad_scale=1.0, R=R, V=V, ldl=ldl, ldd=ldl, ignore_index=ignore_index,
-                logits_f32=int(logits.dtype == torch.float32))
+                logits_f32=int(logits.dtype == torch.float32), label_smoothing=label_smoothing)
     return row_lse, acc
 
 
-def ce_bwd(logits, targets, V, row_lse, acc, dlogits, grad_out=None, grad_scale=1.0, ignore_index=1):
+def ce_bwd(logits, targets, V, row_lse, acc, dlogits, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0):
     R, ldl = logits.shape[0], logits.stride(0)
     call_struct("vacnic_ce_bwd", stream=_stream(), logits=_p(logits), targets=_p(targets), row_lse=_p(row_lse),
                 row_loss=None, loss_sum=acc.data_ptr(), count=acc.data_ptr() + 4, dlogits=_p(dlogits),
                 grad_out=_p(grad_out), grad_scale=grad_scale, R=R, V=V, ldl=ldl, ldd=dlogits.stride(0),
-                ignore_index=ignore_index, logits_f32=int(logits.dtype == torch.float32))
+                ignore_index=ignore_index, logits_f32=int(logits.dtype == torch.float32), label_smoothing=label_smoothing)
 
 
 def zero_(t):
@@ -421,15 +422,20 @@ def zero_(t):
     return t
 
 
-def _lmhead_args(h2, emb16, targets, V, ignore_index, part=None, tl=None, row_lse=None, acc=None):
+def _lmhead_args(h2, emb16, targets, V, ignore_index, part=None, tl=None, row_lse=None, acc=None, bias=None, part_sum=None,
+                 label_smoothing=0.0):
     R, D = h2.shape
-    return _lib.LmheadCeArgs(h=_p(h2), emb=_p(emb16), bias=None, targets=_p(targets), part=_p(part), tl=_p(tl), row_lse=_p(row_lse),
+    return _lib.LmheadCeArgs(h=_p(h2), emb=_p(emb16), bias=_p(bias), targets=_p(targets), part=_p(part), tl=_p(tl), row_lse=_p(row_lse),
                              loss_sum=acc.data_ptr() if acc is not None else None, count=acc.data_ptr() + 4 if acc is not None else None,
-                             R=R, V=V, D=D, ldh=h2.stride(0), lde=emb16.stride(0), part_tiles=(V + 255) // 256, ignore_index=ignore_index)
+                             R=R, V=V, D=D, ldh=h2.stride(0), lde=emb16.stride(0), part_tiles=(V + 255) // 256, ignore_index=ignore_index,
+                             part_sum=_p(part_sum), label_smoothing=label_smoothing)
 
 
-def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1):
-    """fused lm_head + CrossEntropyLoss forward without logits: returns (row_lse [R], acc = {loss_sum, count})."""
+def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1, label_smoothing=0.0, bias=None, part_sum=None):
+    """fused lm_head + CrossEntropyLoss forward without logits: returns (row_lse [R], acc = {loss_sum, count}).
+    label_smoothing > 0: torch's CrossEntropyLoss(label_smoothing=) — the epilogue also keeps the per-tile sums of the logits in
+    `part_sum` ([R, ceil(V / 256)] f32 scratch, allocated when not given); 0.0 is the plain path and never touches it.
+    bias: optional f32 [V] (final_logits_bias)."""
     R = h2.shape[0]
     dev = h2.device
     tiles = (V + 255) // 256
@@ -437,21 +443,39 @@ def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1):
     tl = torch.empty(R, device=dev, dtype=torch.float32)
     row_lse = torch.empty(R, device=dev, dtype=torch.float32)
     acc = torch.empty(2, device=dev, dtype=torch.float32)
-    st = _lmhead_args(h2, emb16, targets, V, ignore_index, part, tl, row_lse, acc)
+    if label_smoothing > 0.0 and part_sum is None:
+        part_sum = torch.empty((R, tiles), device=dev, dtype=torch.float32)
+    if part_sum is not None and (tuple(part_sum.shape) != (R, tiles) or part_sum.dtype != torch.float32 or not part_sum.is_contiguous()
+                                 or part_sum.device != dev):
+        raise ValueError(f"lmhead_ce_fwd: part_sum must be a contiguous float32 [{R}, {tiles}] tensor on {dev}")
+    st = _lmhead_args(h2, emb16, targets, V, ignore_index, part, tl, row_lse, acc, bias=bias, part_sum=part_sum,
+                      label_smoothing=label_smoothing)
     _lib.check(_lib.lib.vacnic_lmhead_ce_fwd(_lib.C.byref(st), _stream()))
     return row_lse, acc
 
 
-def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1):
+def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0, V=None):
+    """per-row operands of lmhead_ce_dlogits: [R, 2] = {lse, coef}; with label_smoothing > 0 (which needs V) [R, 4] =
+    {lse, coef, coef (1 - eps), coef eps / V}.  Pass the same label_smoothing to lmhead_ce_dlogits."""
     R = row_lse.shape[0]
+    if label_smoothing != 0.0:
+        if V is None:
+            raise TypeError("lmhead_ce_rowp: label_smoothing needs V (the uniform term is eps / V)")
+        rowp = torch.empty((R, 4), device=row_lse.device, dtype=torch.float32)
+        call("vacnic_lmhead_ce_rowp_smooth", _p(row_lse), _p(targets), acc.data_ptr() + 4, _p(grad_out), grad_scale, label_smoothing, V,
+             _p(rowp), R, ignore_index, _stream())
+        return rowp
     rowp = torch.empty((R, 2), device=row_lse.device, dtype=torch.float32)
     call("vacnic_lmhead_ce_rowp", _p(row_lse), _p(targets), acc.data_ptr() + 4, _p(grad_out), grad_scale, _p(rowp), R, ignore_index, _stream())
     return rowp
 
 
-def lmhead_ce_dlogits(h2, emb16, targets, V, rowp, dl, col0, ncols, ignore_index=1):
+def lmhead_ce_dlogits(h2, emb16, targets, V, rowp, dl, col0, ncols, ignore_index=1, label_smoothing=0.0, bias=None):
     """dl[:, :round_up(ncols, 8)] = bf16 dlogits of vocabulary columns [col0, col0 + ncols) (logits recomputed on chip)."""
-    st = _lmhead_args(h2, emb16, targets, V, ignore_index)
+    if 0.0 <= label_smoothing < 1.0 and rowp.shape[-1] != (4 if label_smoothing > 0.0 else 2):   # (a bad eps is the library's to reject)
+        raise ValueError(f"lmhead_ce_dlogits: rowp has {rowp.shape[-1]} floats per row; label_smoothing={label_smoothing} reads "
+                         f"{4 if label_smoothing > 0.0 else 2} (build it with lmhead_ce_rowp(label_smoothing=...))")
+    st = _lmhead_args(h2, emb16, targets, V, ignore_index, bias=bias, label_smoothing=label_smoothing)
     _lib.check(_lib.lib.vacnic_lmhead_ce_dlogits(_lib.C.byref(st), col0, ncols, _p(dl), dl.stride(0), _p(rowp), _stream()))
 
 

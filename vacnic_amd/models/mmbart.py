@@ -554,6 +554,7 @@ class BartForMultiModalGeneration(nn.Module):
 
     Extra (MI355X-native) entry: `forward(..., labels=tgt_ids)` fuses lm_head + CrossEntropyLoss(ignore_index=pad)
     and returns `loss` without exposing logits (the reference computes it at TRAIN:287 from materialised logits).
+    `label_smoothing=` (None: config.label_smoothing, default 0.0) makes that loss torch's CrossEntropyLoss(label_smoothing=).
     Call `.finalize(device)` once after loading weights: it moves all parameters into the flat arena."""
 
     def __init__(self, config: VacnicConfig, enc_fusion_layer=None, dim_common=256, img_size=2048, prompt_mlp_type="clipcap",
@@ -636,8 +637,9 @@ class BartForMultiModalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, image_features=None, face_features=None,
                 face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, labels=None, output_logits=None,
-                encoder_outputs=None, output_attentions=None, **unused):
-        """output_attentions=True (None: config.output_attentions, MFULL:1944) adds the attention maps to the returned dict —
+                encoder_outputs=None, output_attentions=None, label_smoothing=None, **unused):
+        """label_smoothing (None: config.label_smoothing) applies to the fused `labels=` loss only; 0.0 is the plain cross entropy.
+        output_attentions=True (None: config.output_attentions, MFULL:1944) adds the attention maps to the returned dict —
         see BartModel.forward.  They are the pre-dropout softmax, fp32, without an autograd graph.  generate() does not return
         maps."""
         if self.arena is None:
@@ -653,7 +655,8 @@ class BartForMultiModalGeneration(nn.Module):
         if labels is not None:
             hl, h = ops.fork(h) if want_logits else (h, None)
             loss, acc = ops.lm_head_ce(hl, self.model.shared.weight, self.emb16_pad, self.model.shared.weight.grad, labels,
-                                       self.V, self.config.pad_token_id)
+                                       self.V, self.config.pad_token_id,
+                                       label_smoothing=self.config.label_smoothing if label_smoothing is None else label_smoothing)
             out["loss"], out["loss_acc"] = loss, acc
         if want_logits:
             lg = ops.linear(h, self.model.shared.weight, self.s_lm)                           # lm_head(h) + final_logits_bias, MFULL:1997

@@ -745,14 +745,14 @@ class LmHeadCeFn(Function):
     (into the tied matrix's gradient rows) GEMMs before the buffer is re-used."""
 
     @staticmethod
-    def forward(ctx, h, anchor, emb16_pad, egrad, targets, V, ignore_index, ge):
+    def forward(ctx, h, anchor, emb16_pad, egrad, targets, V, ignore_index, ge, label_smoothing=0.0):
         _tag(ctx)
         d = h.shape[-1]
         h2 = _c(h).view(-1, d)
         tgt = _c(targets).view(-1)
-        row_lse, acc = K.lmhead_ce_fwd(h2, emb16_pad, tgt, V, ignore_index=ignore_index)
+        row_lse, acc = K.lmhead_ce_fwd(h2, emb16_pad, tgt, V, ignore_index=ignore_index, label_smoothing=label_smoothing)
         out4 = K.combine_losses(acc.data_ptr(), acc.data_ptr() + 4, None, None, 0.0, 0.0, h.device)
-        ctx.misc = (emb16_pad, egrad, V, ignore_index, h2.shape[0], d, h.shape)
+        ctx.misc = (emb16_pad, egrad, V, ignore_index, h2.shape[0], d, h.shape, label_smoothing)
         ctx.save_for_backward(h2, tgt, row_lse, acc)
         ctx.mark_non_differentiable(acc)
         ddp.expect(ge and any(ctx.needs_input_grad), egrad)
@@ -761,8 +761,8 @@ class LmHeadCeFn(Function):
     @_bw
     def backward(ctx, g, _gacc):
         h2, tgt, row_lse, acc = ctx.saved_tensors
-        emb16_pad, egrad, V, ignore_index, R, d, hshape = ctx.misc
-        rowp = K.lmhead_ce_rowp(row_lse, tgt, acc, grad_out=_c(g), grad_scale=1.0, ignore_index=ignore_index)
+        emb16_pad, egrad, V, ignore_index, R, d, hshape, eps = ctx.misc
+        rowp = K.lmhead_ce_rowp(row_lse, tgt, acc, grad_out=_c(g), grad_scale=1.0, ignore_index=ignore_index, label_smoothing=eps, V=V)
         CH = min(LMHEAD_CHUNK, (V + 7) // 8 * 8)
         # dE (the tied matrix's weight gradient) is needed only by AdamW / the reducer: with side streams on it runs on the
         # weight-gradient stream beside the next chunk's dlogits / dh GEMMs, out of the decoder phase's chain (the least busy part of
@@ -776,7 +776,7 @@ class LmHeadCeFn(Function):
             dl = dls[ci % len(dls)]
             if side is not None and ci >= 2:
                 K.fence(streams.wgrad_raw(), K._stream())          # the dE GEMM of chunk ci - 2 has read this buffer
-            K.lmhead_ce_dlogits(h2, emb16_pad, tgt, V, rowp, dl, c0, n, ignore_index=ignore_index)
+            K.lmhead_ce_dlogits(h2, emb16_pad, tgt, V, rowp, dl, c0, n, ignore_index=ignore_index, label_smoothing=eps)
             ec = emb16_pad[c0:c0 + n8]
             # dh += dlogits_c . E_c: a reduction 8-16x longer than the output is wide -> split-K, fp32 accumulate
             K.gemm(dl, ec, R, d, n8, out=dh32, ldx=CH, w_kstrided=True, out_mode=2, split_k=4, fixup=True, tile_hint=128)
@@ -792,11 +792,12 @@ class LmHeadCeFn(Function):
                            split_k=K.wgrad_split(R, tiles))
         dh = K.cast_f32_bf16(dh32)
         ddp.done(egrad)
-        return dh.view(hshape), None, None, None, None, None, None, None
+        return dh.view(hshape), None, None, None, None, None, None, None, None
 
 
-def lm_head_ce(h, anchor, emb16_pad, egrad, targets, V, ignore_index=1):
-    loss, acc = LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled())
+def lm_head_ce(h, anchor, emb16_pad, egrad, targets, V, ignore_index=1, label_smoothing=0.0):
+    """label_smoothing: torch's CrossEntropyLoss(label_smoothing=); 0.0 = the plain loss, bit-identical to the path without the option."""
+    loss, acc = LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled(), float(label_smoothing))
     return loss, acc
 
 

@@ -148,7 +148,8 @@ _PLAN = None          # the PlannedTrainStep being recorded (forward_losses leav
 
 
 def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None):
-    """Forward of one step; returns (total, out4={total, txt, secla, colam}, model_out).  `model` may be the DDP wrapper
+    """Forward of one step; returns (total, out4={total, txt, secla, colam}, model_out).  With config.label_smoothing > 0 `txt` is the
+    smoothed loss, as torch's CrossEntropyLoss(label_smoothing=) reports it.  `model` may be the DDP wrapper
     (like TRAIN:274 `model.module`).  `ready`: optional event after which the batch tensors are valid in HBM; with side
     streams enabled the frozen towers then start on it instead of on the compute stream's tail (= the previous AdamW)."""
     net = model.module if isinstance(model, DistributedDataParallel) else model
@@ -287,7 +288,8 @@ def _model_inputs(net, batch, graphed=False):
 
 @torch.no_grad()
 def eval_epoch(model, batches, device="cuda"):
-    """TRAIN:391-447 / TRAINV:203-250: teacher-forced validation pass in eval mode.  Returns (mean of the per-batch text
+    """TRAIN:391-447 / TRAINV:203-250: teacher-forced validation pass in eval mode.  The validation loss is always the plain NLL
+    (config.label_smoothing is a training-loss option), so best-checkpoint selection stays comparable across runs.  Returns (mean of the per-batch text
     cross-entropy, out_dict) with out_dict[step] = {"logit_output": argmax token ids per sample, "gt_cap": target ids} — the
     reference stores the same two things as decoded strings (tokenizers are outside SURVEY §8).  One host sync per batch
     (the `.item()` of TRAIN:441), like the reference."""
@@ -302,7 +304,7 @@ def eval_epoch(model, batches, device="cuda"):
         tgt = batch["caption_ids"]
         _, tgt_in = K.prep_ids(tgt, cfg.pad_token_id, start_id=cfg.eos_token_id)
         out = net(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in, image_features=feats, labels=tgt,
-                  output_logits=True, add_ner_ffn=True, **kw)
+                  output_logits=True, add_ner_ffn=True, label_smoothing=0.0, **kw)
         lg = out["logits"]
         ids = K.argmax_rows(lg.view(-1, lg.shape[-1]), net.V).view(tgt.shape)
         out_dict[step] = {"logit_output": ids.tolist(), "gt_cap": tgt.tolist()}
