@@ -239,10 +239,9 @@ class DistributedDataParallel(torch.nn.Module):
         cur = K._stream()                                     # launch stream of whatever completed the bucket (compute / branch)
         with K.launch_on(None):                               # (torch's current stream = the compute stream)
             main = K._stream()
-        side = streams.wgrad_raw() if streams.wgrad_stream() is not None else main
-        for src in {cur, main, streams.raw("branch") if streams.branch_stream() is not None else None}:
-            if src is not None and src != side:
-                K.fence(src, side)
+        side = streams.raw("wgrad") or main
+        for src in {cur, main, streams.raw("branch") or main}:
+            K.fence(src, side)                                # (a no-op where src is side)
         with K.launch_on(side, fence=False):
             if s16 is not None:
                 K.cast_f32_bf16(g, s16)

@@ -42,8 +42,12 @@ class launch_on:
 
     fence=True (default): the side stream first waits for everything enqueued on torch's current stream so far.  torch's
     allocator believes every block lives on the current stream and hands a freed block out again at once; a kernel launched on
-    the side stream into such a block must not overtake the compute-stream kernels that were still using it.  (Blocks a
-    side-stream kernel uses are held by the keep-list until the compute stream has joined that stream: kernels._p.)"""
+    the side stream into such a block must not overtake the compute-stream kernels that were still using it.
+
+    Lifetime: every tensor a kernel wrapper is handed inside the section goes onto the side-stream keep-list (_p) and stays
+    referenced until the compute stream has joined that stream (streams.join_all).  The list has no other
+    writer: call sites keep nothing by hand, so a wrapper that may run on a side stream passes every
+    tensor of the call through _p."""
 
     def __init__(self, raw, fence=True):
         self.raw, self.fence = raw, fence
@@ -67,6 +71,7 @@ _KEEP = None            # streams.py's keep-list: tensors handed to a kernel on 
 
 
 def _p(t):
+    """device address of `t` for the C-ABI; inside a launch_on section it also puts `t` on the keep-list (see launch_on)."""
     if t is None:
         return None
     if not t.is_cuda:

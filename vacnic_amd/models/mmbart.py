@@ -229,11 +229,11 @@ class BartEncoderLayer(nn.Module):
             # The image / face / name branches (MFULL:647-691) are a dozen small kernels over 20-80 tokens per sample and are
             # independent of the text self-attention block of this layer; with side streams on (training only) they run on
             # the branch stream beside it and join before the cross-attention that consumes their output.
-            br = streams.branch_stream() if (torch.is_grad_enabled() and hidden_states.is_cuda) else None
-            if br is not None:
+            br_raw = streams.raw("branch") if (torch.is_grad_enabled() and hidden_states.is_cuda) else None
+            if br_raw is not None:
                 # the branch ops are launched on the branch stream through kernels.launch_on, and the tensors that cross between
                 # the two streams go through ops.stream_hop (fence forward, mirrored fence in backward)
-                main_raw, br_raw = K._stream(), streams.raw("branch")
+                main_raw = K._stream()
                 if not on_branch:
                     ins = [t for t in (hidden_states_img, hidden_states_face, hidden_states_ner) if t is not None]
                     outs = list(ops.stream_hop(main_raw, br_raw, *ins))
@@ -285,7 +285,7 @@ class BartEncoderLayer(nn.Module):
                 kv = self.cross_attn_img_ner.project_kv(kv)        # k|v projection of the [img ; prefix] tokens: also off the text chain
             a, r, self_map = self.self_attn(h, key_mask=key_mask, skip=True, output_attentions=oa)
             h = self._ln(a, r, self.self_attn_layer_norm)                                          # :697-707
-            if br is not None:
+            if br_raw is not None:
                 (kv,) = ops.stream_hop(br_raw, main_raw, kv)
             a, r, cross_map = self.cross_attn_img_ner(h, kv=kv, key_mask=None, skip=True, output_attentions=oa)
             h = self._ln(a, r, self.img_ner_attn_layer_norm)                                       # :711-723
@@ -405,7 +405,7 @@ class BartEncoder(nn.Module):
             img = ops.linear(img, self.visual_map.weight, self.s_vmap)                                   # :1277-1278
         # img_ner_mask_cross is all ones (:1280-1296) -> no key mask on the visual/name cross-attention
         # with side streams on: from the first fusion layer on the image / face / name streams live on the branch stream
-        use_branch = streams.branch_stream() is not None and torch.is_grad_enabled() and h.is_cuda
+        use_branch = streams.raw("branch") is not None and torch.is_grad_enabled() and h.is_cuda
         on_branch = False
         for idx, layer in enumerate(self.layers):
             fused = idx in self.fusion_layer

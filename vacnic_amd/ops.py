@@ -11,6 +11,8 @@ Conventions
     differentiable.
   * a tensor consumed by two ops goes through fork() so the gradient fan-in is our add kernel.
 """
+import contextlib
+
 import torch
 from torch.autograd import Function
 
@@ -113,6 +115,13 @@ class StreamHopFn(Function):
         return (None, None) + gs
 
 
+def _on_wgrad():
+    """with _on_wgrad(): launch on the weight-gradient stream — nothing changes when side streams are off.  No fence on entry:
+    the caller has ordered that stream behind its producer (K.fence(K._stream(), streams.raw("wgrad"))) where that is needed."""
+    raw = streams.raw("wgrad")
+    return K.launch_on(raw, fence=False) if raw is not None else contextlib.nullcontext()
+
+
 def stream_hop(src, dst, *xs):
     """xs, usable on stream dst (see StreamHopFn).  Tensors that need no gradient are fenced without a graph node."""
     if src == dst:
@@ -174,19 +183,10 @@ class _WgradQueue:
             return
         for _, _, sp in jobs:
             self.dst.discard(sp.wgrad.data_ptr())
-        packed = [(dy, x, sp.wgrad, sp.bgrad) for dy, x, sp in jobs]
-        side = streams.wgrad_stream()
-        if side is None:
-            K.wgrad_group(packed)
-            for _, _, sp in jobs:
-                ddp.done(sp.wgrad, sp.bgrad)
-            return
-        with K.launch_on(streams.wgrad_raw(), fence=False):      # (every job fenced its producer -> wgrad stream when it was queued)
-            K.wgrad_group(packed)
+        with _on_wgrad():                        # (every job fenced its producer -> wgrad stream when it was queued)
+            K.wgrad_group([(dy, x, sp.wgrad, sp.bgrad) for dy, x, sp in jobs])
         for _, _, sp in jobs:
             ddp.done(sp.wgrad, sp.bgrad)
-        for dy, x, _ in jobs:
-            streams.keep(dy, x)
 
     def flush(self):
         self.armed = False
@@ -229,23 +229,15 @@ def _groupable(dy2d, x2d, spec, M):
 def _wgrad(dy2d, x2d, spec, M):
     """spec.wgrad[N,K] += dy^T x ; spec.bgrad[N] += colsum(dy).  Off the critical path: issued on the weight-gradient
     side stream when streams are enabled (each weight has exactly one writer op, so there is no cross-stream race)."""
-    side = streams.wgrad_stream()
-    group = _groupable(dy2d, x2d, spec, M)
-    if side is None:
-        if group:
-            _WGQ.add(dy2d, x2d, spec, M)
-            return
-        _wgrad_impl(dy2d, x2d, spec, M)
-        ddp.done(spec.wgrad, spec.bgrad)
-        return
-    K.fence(K._stream(), streams.wgrad_raw())              # dy / x were produced on the stream this backward node launches on
-    if group:
+    side = streams.raw("wgrad")
+    if side is not None:
+        K.fence(K._stream(), side)                         # dy / x were produced on the stream this backward node launches on
+    if _groupable(dy2d, x2d, spec, M):
         _WGQ.add(dy2d, x2d, spec, M)
         return
-    with K.launch_on(streams.wgrad_raw(), fence=False):
+    with _on_wgrad():                                # (dy / x stay alive until the compute stream joins it: kernels._p)
         _wgrad_impl(dy2d, x2d, spec, M)
     ddp.done(spec.wgrad, spec.bgrad)
-    streams.keep(dy2d, x2d)                                # alive until the compute stream joins the side stream
 
 
 def _wgrad_impl(dy2d, x2d, spec, M):
@@ -613,10 +605,9 @@ class AddLnFn(Function):
         x, res, mean, rstd = ctx.saved_tensors
         gamma, beta = ctx.gb
         # the fold of the LayerNorm parameter gradients (needed by AdamW / the reducer only) rides on the weight-gradient stream
-        side = streams.wgrad_raw() if streams.wgrad_stream() is not None else None
         dx, dres = K.add_ln_bwd(_c(dout), x, res, gamma, mean, rstd, gamma.grad, beta.grad, p_drop=ctx.p, seed=ctx.seed,
                                 seed_dev=Rng.device_counter() if ctx.p > 0 else None,
-                                need_dres=ctx.has_res and ctx.needs_input_grad[1], fold_on=side)
+                                need_dres=ctx.has_res and ctx.needs_input_grad[1], fold_on=streams.raw("wgrad"))
         ddp.done(gamma.grad, beta.grad)
         return (dx if ctx.needs_input_grad[0] else None), (dres if ctx.has_res and ctx.needs_input_grad[1] else None), None, None, None, None, None
 
@@ -643,10 +634,11 @@ class EmbedLnFn(Function):
     def backward(ctx, dout):
         ids, mean, rstd = ctx.saved_tensors
         tok, pos, gamma, beta, scale, p, seed, pad = ctx.args
-        if streams.wgrad_stream() is not None:
+        side = streams.raw("wgrad")
+        if side is not None:
             # the tied matrix has another writer on the weight-gradient stream (the LM head's dE GEMMs: plain read-modify-write of
             # the same rows this kernel adds to with atomics): order behind it
-            K.fence(streams.wgrad_raw(), K._stream())
+            K.fence(side, K._stream())
         K.embed_ln_bwd(ids, tok.w16, pos.w16, _c(dout), gamma, mean, rstd, tok.grad, pos.grad, gamma.grad, beta.grad,
                        embed_scale=scale, padding_idx=pad, p_drop=p, seed=seed, seed_dev=Rng.device_counter() if p > 0 else None)
         ddp.done(tok.grad, pos.grad, gamma.grad, beta.grad)
@@ -767,7 +759,7 @@ class LmHeadCeFn(Function):
         # dE (the tied matrix's weight gradient) is needed only by AdamW / the reducer: with side streams on it runs on the
         # weight-gradient stream beside the next chunk's dlogits / dh GEMMs, out of the decoder phase's chain (the least busy part of
         # the step).  Two dlogits buffers alternate; a chunk's buffer is reused only after the side stream has read it.
-        side = streams.wgrad_stream() if egrad is not None else None
+        side = streams.raw("wgrad") if egrad is not None else None
         dls = [torch.empty((R, CH), device=h2.device, dtype=BF16) for _ in range(2 if side is not None else 1)]
         dh32 = K.zero_(torch.empty((R, d), device=h2.device, dtype=torch.float32))
         for ci, c0 in enumerate(range(0, V, CH)):
@@ -775,7 +767,7 @@ class LmHeadCeFn(Function):
             n8 = (n + 7) // 8 * 8                                  # dlogits pad columns are written as zeros; E's pad rows are zero
             dl = dls[ci % len(dls)]
             if side is not None and ci >= 2:
-                K.fence(streams.wgrad_raw(), K._stream())          # the dE GEMM of chunk ci - 2 has read this buffer
+                K.fence(side, K._stream())                         # the dE GEMM of chunk ci - 2 has read this buffer
             K.lmhead_ce_dlogits(h2, emb16_pad, tgt, V, rowp, dl, c0, n, ignore_index=ignore_index, label_smoothing=eps)
             ec = emb16_pad[c0:c0 + n8]
             # dh += dlogits_c . E_c: a reduction 8-16x longer than the output is wide -> split-K, fp32 accumulate
@@ -783,11 +775,8 @@ class LmHeadCeFn(Function):
             if egrad is not None:                                  # dE[c0:c0+n] += dlogits_c^T h
                 tiles = ((n + 127) // 128) * ((d + 127) // 128)
                 if side is not None:
-                    K.fence(K._stream(), streams.wgrad_raw())      # dlogits of this chunk (and h) are ready
-                    with K.launch_on(streams.wgrad_raw(), fence=False):
-                        K.gemm(dl, h2, n, d, R, out=egrad[c0:c0 + n], ldx=CH, ldw=d, ldo=d, x_kstrided=True, w_kstrided=True, out_mode=2,
-                               split_k=K.wgrad_split(R, tiles))
-                else:
+                    K.fence(K._stream(), side)                     # dlogits of this chunk (and h) are ready
+                with _on_wgrad():
                     K.gemm(dl, h2, n, d, R, out=egrad[c0:c0 + n], ldx=CH, ldw=d, ldo=d, x_kstrided=True, w_kstrided=True, out_mode=2,
                            split_k=K.wgrad_split(R, tiles))
         dh = K.cast_f32_bf16(dh32)

@@ -11,15 +11,20 @@ streams so the hardware can schedule their workgroups into those bubbles:
 Side-stream work is launched through kernels.launch_on(raw stream) and every cross-stream edge is a kernels.fence():
 torch (allocator, autograd engine) sees ONE stream, so no synchronisation is hidden inside torch and the step's launch
 sequence, fences included, can be recorded into a launch plan (training.PlannedTrainStep).  Because the allocator only
-knows the compute stream, tensors consumed on a side stream are kept alive by `keep()` until the compute stream has joined
-that stream (`join_all`), NOT by Tensor.record_stream(): with recorded blocks outstanding the caching allocator polls their
-events on every allocation, which cost ~14 us per torch.empty (16 ms of host time per step).
+knows the compute stream, tensors consumed on a side stream are kept alive by the keep-list until the compute stream has
+joined that stream (`join_all`), NOT by Tensor.record_stream(): with recorded blocks outstanding the caching allocator polls
+their events on every allocation, which cost ~14 us per torch.empty (16 ms of host time per step).  The list has one owner:
+kernels._p appends every tensor handed to a kernel inside a launch_on section, so no call site keeps tensors by hand.
+
+`raw(name)` is the one way to a side stream's handle (None when side streams are off: the caller then launches where it stands);
+the torch Stream objects (`aux_stream()` ...) are for the places that need one: wait_event, torch.cuda.stream, torch collectives.
 """
 import torch
 
 from . import kernels as _K
 
-_state = {"enabled": False, "wgrad": None, "aux": None, "vit": None, "branch": None, "wgrad_raw": None, "keep": []}
+_state = {"enabled": False, "wgrad": None, "aux": None, "vit": None, "branch": None, "keep": []}
+_raw = {}                 # name -> hipStream_t (Stream.cuda_stream is a property that builds a Python int on every read)
 _K._KEEP = _state["keep"]
 
 
@@ -27,19 +32,18 @@ def enable(flag=True):
     _state["enabled"] = bool(flag) and torch.cuda.is_available()
     if _state["enabled"] and _state["wgrad"] is None:
         _state["wgrad"] = torch.cuda.Stream()
-        _state["wgrad_raw"] = _state["wgrad"].cuda_stream
         _state["aux"] = torch.cuda.Stream()
         # the two frozen towers share ONE stream (ViT first: the student needs it first): same-box A/B 65.1 vs 66.0 ms/step
         # (profiles/r3_step_ab_towers.txt) — two towers running beside each other AND beside the backward chain take more CUs away
         # from that chain than their overlap buys
         _state["vit"] = _state["aux"]
         _state["branch"] = torch.cuda.Stream()
+        _raw.update((n, _state[n].cuda_stream) for n in ("wgrad", "aux", "vit", "branch"))
 
 
 def raw(name):
     """raw hipStream_t of side stream 'wgrad' | 'aux' | 'vit' | 'branch' (None when side streams are off)."""
-    s = _state[name] if _state["enabled"] else None
-    return s.cuda_stream if s is not None else None
+    return _raw[name] if _state["enabled"] else None
 
 
 def enabled():
@@ -48,18 +52,6 @@ def enabled():
 
 def wgrad_stream():
     return _state["wgrad"] if _state["enabled"] else None
-
-
-def wgrad_raw():
-    return _state["wgrad_raw"]
-
-
-def keep(*tensors):
-    """hold references to tensors a side stream is still reading; released by join_all()."""
-    k = _state["keep"]
-    k.extend(tensors)
-    if len(k) > (1 << 18):                    # (only a caller that never joins gets here)
-        join_all()
 
 
 def pending_keep():
@@ -72,10 +64,6 @@ def branch_stream():
     20-80 tokens per sample that occupy a fraction of the GPU) — they run beside the text self-attention block of the same
     layer, forward and backward (the autograd engine replays each node on the stream of its forward)."""
     return _state["branch"] if _state["enabled"] else None
-
-
-def side_streams():
-    return [s for s in (_state["wgrad"], _state["aux"], _state["vit"], _state["branch"]) if s is not None] if _state["enabled"] else []
 
 
 def aux_stream():
@@ -100,6 +88,6 @@ def join_all(skip_wgrad=False):
         for name in ("wgrad", "aux", "branch"):          # (the ViT runs on the aux stream)
             if name == "wgrad" and skip_wgrad:
                 continue
-            _K.fence(_state[name].cuda_stream, cur)
+            _K.fence(_raw[name], cur)
         if not skip_wgrad:
             _state["keep"].clear()

@@ -147,6 +147,31 @@ def image_feature_index(cfg):
 _PLAN = None          # the PlannedTrainStep being recorded (forward_losses leaves marks in it)
 
 
+def _tower_host(what, towers, batch=None, ready=None, by_plan=False):
+    """The host's part in a step whose frozen towers are hipGraph replays (FrozenTowerGraphs), each action written once:
+      'launch'           start both replays for (batch, ready); the compute stream waits for the image feature only
+      'join_guide'       the compute stream waits for the guide's output (before the CoLaM loss)
+      'towers_consumed'  the towers' static outputs have been read: the next replay may overwrite them
+    This is torch-side stream work, which a launch plan cannot hold.  An eager step acts where it stands; while a plan is being
+    recorded the point goes to the plan (PlannedTrainStep.mark), which acts through this function (by_plan=True) at recording
+    and at the same point of every replay."""
+    if _PLAN is not None and not by_plan:
+        _PLAN.mark(what)
+    elif what == "launch":
+        towers.launch(batch, ready)
+        torch.cuda.current_stream().wait_event(towers.ev_vit)
+        if not by_plan:
+            # an eager step hands the tower streams a loader-owned batch, which the allocator may recycle once the caller drops it
+            # (a plan's caller keeps its batches resident: no record_stream there — see streams on the allocator's polling cost)
+            batch["article_ids"].record_stream(streams.aux_stream())
+            batch["caption_ids"].record_stream(streams.aux_stream())
+            batch["img_tensor"].record_stream(streams.vit_stream())
+    elif what == "join_guide":
+        torch.cuda.current_stream().wait_stream(streams.aux_stream())
+    elif what == "towers_consumed":
+        towers.mark_consumed()
+
+
 def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None):
     """Forward of one step; returns (total, out4={total, txt, secla, colam}, model_out).  With config.label_smoothing > 0 `txt` is the
     smoothed loss, as torch's CrossEntropyLoss(label_smoothing=) reports it.  `model` may be the DDP wrapper
@@ -169,20 +194,13 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
         src_mask, _ = K.prep_ids(src, cfg.pad_token_id)                                      # create_src_mask_bart, TRAIN:268
         tgt_mask, tgt_in = K.prep_ids(tgt, cfg.pad_token_id, start_id=cfg.eos_token_id)     # shift_tokens_right, TRAIN:267,296
         img_cls = extract_clip_img_feat(net.clip_model, batch["img_tensor"])[feat]            # TRAIN:274-276
-    elif towers is not None and _PLAN is not None:
-        # recording a launch plan around the tower graphs (PlannedTrainStep): the graphs are replayed by the host before each plan
-        # replay and joined at the plan's marks; the id preprocessing runs inside the plan, on the compute stream
+    elif towers is not None:
+        # frozen towers as two hipGraph replays on their side streams (FrozenTowerGraphs), started and joined by the host
+        # (_tower_host); the id preprocessing runs on the compute stream (inside the plan, when one is recorded)
+        _tower_host("launch", towers, batch, ready)
         src_mask, _ = K.prep_ids(src, cfg.pad_token_id)
         tgt_mask, tgt_in = K.prep_ids(tgt, cfg.pad_token_id, start_id=cfg.eos_token_id)
         img_cls, gh = towers.img_cls, towers.gh
-    elif towers is not None:
-        # frozen towers as two hipGraph replays on their side streams (FrozenTowerGraphs)
-        src_mask, tgt_mask, tgt_in, ev_prep = towers.launch(batch, ready)
-        main.wait_event(ev_prep)
-        main.wait_event(towers.ev_vit)
-        img_cls, gh = towers.img_cls, towers.gh
-        for tns in (src_mask, tgt_mask, tgt_in):
-            tns.record_stream(main)
     else:
         # id preprocessing + frozen guide forward + frozen ViT on the side streams: they depend only on the batch, so they fill
         # the bubbles of the main chain (and of the previous step's AdamW); launched through kernels.launch_on and ordered by
@@ -214,19 +232,15 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
     txt = out["loss"]
     colam = secla = None
     if guide is not None:
-        if towers is not None and _PLAN is not None:
-            _PLAN.mark("join_guide")             # the host makes the compute stream wait for the guide graph here
-        elif aux is not None and towers is None:
-            K.fence(streams.raw("aux"), K._stream())
-        elif aux is not None:
-            main.wait_stream(aux)                # (eager tower graphs)
-        else:
+        if aux is None:
             gh = guide(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in)["decoder_hidden_states"][-1]   # TRAIN:293-294
+        elif towers is not None:
+            _tower_host("join_guide", towers)
+        else:
+            K.fence(streams.raw("aux"), K._stream())
         colam = ops.ColamFn.apply(out["decoder_hidden_states"][-1], gh, tgt_mask, args.margin, args.alpha)        # TRAIN:296-307
-    if towers is not None and _PLAN is not None:
-        _PLAN.mark("towers_consumed")
-    elif towers is not None:
-        towers.mark_consumed()               # static img_cls / gh have been read: the next replay may overwrite them
+    if towers is not None:
+        _tower_host("towers_consumed", towers)
     if args.use_secla and not args.no_mapping and not cfg.only_image:
         enc = net.model.encoder
         ln = enc.layernorm_embedding_ner
@@ -255,8 +269,6 @@ def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towe
     # bucket's own event — joining the whole stream here would hold AdamW back until the LAST collective has finished
     pipelined = isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None
     streams.join_all(skip_wgrad=pipelined)   # side streams -> compute stream
-    if _PLAN is not None and _PLAN.towers is not None:
-        _PLAN.mark("backward_done")          # (the host can start the next step's guide graph behind this point)
     if isinstance(model, DistributedDataParallel):
         model.reduce_and_step(optimizer, clip)       # all-reduce tail overlapped with the optimizer of the finished buckets
         if pipelined:
@@ -406,7 +418,6 @@ class PlannedTrainStep:
         from . import _lib
         from . import ddp as _ddp
         self.towers = towers
-        self.ev_bwd = None
         self.static = {k: v.clone() for k, v in example_batch.items()}
         for _ in range(warmup):                              # eager: lazy buffers, kernel loading, allocator warm-up
             train_step(model, guide, optimizer, self.static, args, None, towers)
@@ -441,10 +452,12 @@ class PlannedTrainStep:
         self.commands = int(_lib.lib.vacnic_plan_size(self.handle))
 
     def mark(self, what):
-        """called by forward_losses while recording: the host acts at this point of every replay."""
+        """called by _tower_host while recording: the host acts at this point of every replay.  ('launch' is host work AHEAD of
+        the plan, not a point in it: _before has done it, and does it before every replay.)"""
         from . import _lib
-        self.marks.append((int(_lib.lib.vacnic_plan_mark()), what))
-        self._at(what)
+        if what != "launch":
+            self.marks.append((int(_lib.lib.vacnic_plan_mark()), what))
+            self._at(what)
 
     def host(self, fn):
         """recording: register `fn` as a host action at this point of the plan and run it now, unrecorded (whatever it launches
@@ -459,20 +472,13 @@ class PlannedTrainStep:
 
     def _before(self, batch=None, ready=None):
         if self.towers is not None:
-            late = self.ev_bwd if __import__("os").environ.get("VACNIC_GUIDE_LATE", "0") == "1" else None
-            self.towers.launch_graphs(batch if batch is not None else self.static, ready, guide_after=late)
-            torch.cuda.current_stream().wait_event(self.towers.ev_vit)         # the student's encoder needs the image feature
+            _tower_host("launch", self.towers, batch if batch is not None else self.static, ready, by_plan=True)
 
     def _at(self, what):
         if callable(what):
             what()
-        elif what == "join_guide":
-            torch.cuda.current_stream().wait_stream(streams.aux_stream())
-        elif what == "towers_consumed":
-            self.towers.mark_consumed()
-        elif what == "backward_done":
-            self.ev_bwd = torch.cuda.Event()
-            self.ev_bwd.record()
+        else:
+            _tower_host(what, self.towers, by_plan=True)
 
     def __call__(self, batch, ready=None):
         """ready: optional event after which `batch` is resident in HBM (the tower graphs then start on it instead of behind the
@@ -509,7 +515,7 @@ class FrozenTowerGraphs:
 
     Static buffers: inputs are copied in on the tower's stream right before the replay; the outputs (`gh`, `img_cls`) are
     read by the main chain only during the forward pass, so the next replay waits for the `consumed` event recorded
-    after the CoLaM forward (write-after-read), and the id masks the backward needs are fresh tensors every step."""
+    after the CoLaM forward (write-after-read); the id masks the student needs are made by the step itself, on the compute stream."""
 
     def __init__(self, net, guide, example_batch):
         cfg = net.config
@@ -550,46 +556,12 @@ class FrozenTowerGraphs:
                 self.img_cls = vit_body()
         torch.cuda.synchronize()
 
-    def launch(self, batch, ready):
-        """enqueue id preprocessing (eager, fresh tensors) and both tower replays on their streams."""
+    def launch(self, batch, ready=None):
+        """enqueue both tower replays on their streams; the guide's id inputs are derived there, in place, from the batch."""
         aux, vis = streams.aux_stream(), streams.vit_stream()
         main = torch.cuda.current_stream()
         for s_ in (aux, vis):
-            if ready is None:
-                s_.wait_stream(main)
-            else:
-                s_.wait_event(ready)
-            if self.consumed is not None:
-                s_.wait_event(self.consumed)
-        src, tgt = batch["article_ids"], batch["caption_ids"]
-        with torch.cuda.stream(aux):
-            src_mask, _ = K.prep_ids(src, self.pad)
-            tgt_mask, tgt_in = K.prep_ids(tgt, self.pad, start_id=self.start)
-            ev_prep = torch.cuda.Event()
-            ev_prep.record(aux)
-        with torch.cuda.stream(vis):                 # the student's encoder input needs the image feature: ViT goes first
-            self.img_s.copy_(batch["img_tensor"], non_blocking=True)
-            self.g_vit.replay()
-            self.ev_vit = torch.cuda.Event()
-            self.ev_vit.record(vis)                  # (the towers may share one stream: wait for THIS, not for the stream's tail)
-        if self.g_guide is not None:
-            with torch.cuda.stream(aux):             # the guide's output is needed only by the CoLaM loss
-                self.src_s.copy_(src, non_blocking=True)
-                self.mask_s.copy_(src_mask, non_blocking=True)
-                self.tgtin_s.copy_(tgt_in, non_blocking=True)
-                self.g_guide.replay()
-        for tns in (src, tgt):
-            tns.record_stream(aux)
-        batch["img_tensor"].record_stream(vis)
-        return src_mask, tgt_mask, tgt_in, ev_prep
-
-    def launch_graphs(self, batch, ready=None, guide_after=None):
-        """both tower replays only (a launch plan computes the id masks itself): the guide's id inputs are derived here on its own
-        stream from the batch."""
-        aux, vis = streams.aux_stream(), streams.vit_stream()
-        main = torch.cuda.current_stream()
-        for s_ in (aux, vis):
-            # the towers read the CALLER's batch (resident: `ready`, or ordered on the compute stream), not the plan's static copy,
+            # the towers read the CALLER's batch (resident: `ready`, or ordered on the compute stream), not a plan's static copy,
             # so they need not queue behind the previous step's tail on the compute stream
             if ready is None:
                 s_.wait_stream(main)
@@ -597,15 +569,13 @@ class FrozenTowerGraphs:
                 s_.wait_event(ready)
             if self.consumed is not None:
                 s_.wait_event(self.consumed)
-        with torch.cuda.stream(vis):
+        with torch.cuda.stream(vis):                 # the student's encoder input needs the image feature: ViT goes first
             self.img_s.copy_(batch["img_tensor"], non_blocking=True)
             self.g_vit.replay()
             self.ev_vit = torch.cuda.Event()
-            self.ev_vit.record(vis)
+            self.ev_vit.record(vis)                  # (the towers may share one stream: wait for THIS, not for the stream's tail)
         if self.g_guide is not None:
-            with torch.cuda.stream(aux):
-                if guide_after is not None:
-                    aux.wait_event(guide_after)      # the guide (needed only at the CoLaM loss) runs beside the previous AdamW, not its backward
+            with torch.cuda.stream(aux):             # the guide's output is needed only by the CoLaM loss
                 self.src_s.copy_(batch["article_ids"], non_blocking=True)
                 K.prep_ids_into(self.src_s, self.mask_s, None, self.pad)
                 K.prep_ids_into(batch["caption_ids"], None, self.tgtin_s, self.pad, self.start)
