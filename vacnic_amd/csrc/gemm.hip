@@ -7,7 +7,9 @@
 // Design (CDNA4): block tile BMxBN with WMxWN waves, each wave a (BM/WM)x(BN/WN) sub-tile of v_mfma_f32_16x16x32_bf16
 // tiles.  Configurations (chosen per launch by the host cost model below, or forced by tile_hint):
 //   256x256, 8 waves (2x4, 128x64 per wave), 32-wide K stages in a 4-slot LDS ring (128 KiB, one block per CU), PING-PONG
-//            K loop: the two waves of every SIMD alternate MFMA and LDS/DMA phases — the large training GEMMs;
+//            K loop: the two waves of every SIMD alternate MFMA and LDS/DMA phases — the large training GEMMs (hint 256);
+//            the same tile on the 8-PHASE counted-wait loop (64-wide K-tiles as four half-tiles, prefetch in flight across
+//            barriers; gemm_kernel.h p8_loop) — the forward layout (hint 258);
 //   128x128, 4 waves, 64-wide K tiles, two blocks per CU, software-pipelined loop (barrier in the middle of the tile's MFMAs),
 //            register->global epilogue — when that fills the chip better;
 //   64x128,  4 waves, 4-deep ring — small latency-bound problems;   256x128 ping-pong (hint 264);
@@ -338,7 +340,11 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
     const double c = cfg_cost(kCfgs[i], a->M - rem, a->N, kper, z) + cfg_cost(kCfgs[2], rem, a->N, kper, z);
     if (c < 0.85 * split_cost) { split_cost = c; split_cfg = i; m_main = a->M - rem; }
   }
-  if (split_cfg < 0) return gemm_one(a, kCfgs[best].hint, stream);
+  // loop of the 256 x 256 tile: the 8-phase counted-wait loop (hint 258) where it exists and measured faster — the forward layout
+  // without fused dropout (profiles/gemm_8phase_tile_ab.txt: every forward shape); the ping-pong loop (hint 256) everywhere else
+  const bool fwd8 = !a->x_kstrided && !a->w_kstrided && a->drop_p == 0.f;
+  auto loop_of = [&](int hint) { return hint == 256 && fwd8 ? 258 : hint; };
+  if (split_cfg < 0) return gemm_one(a, loop_of(kCfgs[best].hint), stream);
   vacnic_gemm_args main_a = *a, tail_a = *a;
   main_a.M = m_main;
   tail_a.M = a->M - m_main;
@@ -350,7 +356,7 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
   if (a->dact_src) tail_a.dact_src = (const char*)a->dact_src + m_main * a->ldo * 2;
   if (a->residual) tail_a.residual = (const char*)a->residual + m_main * a->ldo * 2;
   if (a->xsum) tail_a.xsum = a->xsum + m_main;
-  if (int e = gemm_one(&main_a, kCfgs[split_cfg].hint, stream)) return e;
+  if (int e = gemm_one(&main_a, loop_of(kCfgs[split_cfg].hint), stream)) return e;
   return gemm_one(&tail_a, kCfgs[2].hint, stream);
 }
 
@@ -448,6 +454,7 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
   if (force == 261) return launch_t261(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (force == 262) return launch_t262(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (force == 264) return launch_t264(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong, half-width tile
+  if (force == 258 && !ce_mode) return launch_t258(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // 256x256, 8-phase counted-wait loop (forward layout)
   if (ce_mode && ce_smooth) return launch_t256cels(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // label smoothing: its own kernel
   if (ce_mode) return launch_t256ce(p, a->x_kstrided, a->w_kstrided, zsplits, s);
   if (big) return launch_t256(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong loop

@@ -247,6 +247,143 @@ __device__ __forceinline__ void lds_barrier() {
 template <int N>
 __device__ __forceinline__ void wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// 8-phase counted-wait K loop of the 256 x 256 tile (8 waves as 2 x 4, 128 x 64 outputs per wave, both operands K-contiguous).
+// A 64-wide K-tile is four HALF-TILES of 128 rows x 64 k (16 KiB each): W0, X0, W1, X1, where X half h holds, for each wave
+// row-group wm, the 64 rows of its fragments a = 4h .. 4h+3, and W half h, for each wave column wn, the 32 rows of b = 2h, 2h+1 —
+// so every wave reads a quarter (X) / an eighth (W) of every half-tile, and the MFMAs of one (X half, W half) pair are one
+// quadrant of the wave's accumulators.  LDS = 2 buffers (K-tile parity) x {W0, X0, W1, X1} = 128 KiB.
+// A half-tile is 16 subtiles of 16 rows x 32 k (1 KiB = one LDS-DMA instruction, 64-B rows); inside a subtile the 16-B chunk
+// index is XOR-ed with 2 * bit 3 of the row (byte ^= ((byte >> 9) & 1) << 5, "st_16x32") on the DMA SOURCE address and again
+// on the fragment read.  Wave w stages row block w of each half-tile (two instructions: k 0..31, 32..63).
+//
+// One K-tile = four phases, one half-tile of prefetch (2 DMA instructions per wave) per phase, 7 half-tiles ahead:
+//     phase | fragment reads (ds_read_b128)  | stages (tile, half) | MFMAs (16 = quadrant x K 64)
+//       1   | W0 (4), then X0 (8)            | t+1, X1             | X0 x W0
+//       2   | W1 (4)                         | t+2, W0             | X0 x W1
+//       3   | X1 (8, over X0's registers)    | t+2, X0             | X1 x W1
+//       4   | -                              | t+2, W1             | X1 x W0      + vmcnt(6) before its first barrier
+// Each phase: reads | DMA | [vmcnt(6)] | barrier | lgkmcnt(0) | 16 MFMAs | barrier.  Waves 4..7 (the SIMD partners of 0..3) run
+// one barrier behind waves 0..3, so one group's reads and DMA issue overlap the other group's MFMAs.
+// Counts (per wave, loads retire in issue order): at phase 4 of tile t the half-tiles up to (t+2, W1) have been issued;
+// vmcnt(6) leaves the three of tile t+2 in flight, so all of tile t+1 has landed — for this wave; the phase's barriers extend
+// that to every wave, and tile t+1 is read from the NEXT phase on (both groups have then passed the barrier that follows the
+// later group's wait).  Write-after-read: a slot is restaged two phases after its last read (X0, W1, X1), which covers the
+// one-barrier stagger; W0, read first in phase 1 and restaged in phase 2, is retired by the lgkmcnt(8) ahead of phase 1's
+// first barrier (the four W0 reads are issued first; LDS reads return in order).  The loads are issued unconditionally (past
+// the end of K they are out of range: zero fill into a slot nobody reads again), so 6 is THE count, in the prologue (7
+// half-tiles, vmcnt(6): tile 0 landed) as in the loop; the caller drains with vmcnt(0) before it reuses the LDS.
+// Every accumulator receives the same MFMAs in the same ascending-k order as in the other loops: results are bit-identical.
+template <int FB, int FA>
+__device__ __forceinline__ void p8_loop(f32x4 (&acc)[FB][FA], char* smem, __amdgpu_buffer_rsrc_t xs, __amdgpu_buffer_rsrc_t ws,
+                                        int m0, int n0, int RX, int RW, int kbeg, int kend, int ntile, int ldx, int ldw,
+                                        int wave, int lane) {
+  static_assert(FB == 4 && FA == 8, "128 x 64 outputs per wave");
+  constexpr int HALF = 16384, BUF = 4 * HALF;
+  constexpr int SLOT_W0 = 0, SLOT_X0 = HALF, SLOT_W1 = 2 * HALF, SLOT_X1 = 3 * HALF;
+  const int wm = wave & 1, wn = wave >> 1;
+  // ---- staging: this lane's row of the subtile, its (un-swizzled) k chunk, and the byte offset of that element at k = 0
+  const int sr = lane >> 2, sc = (lane & 3) ^ (((lane >> 5) & 1) << 1);
+  unsigned xoff[2], woff[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int gx = m0 + (wave >> 2) * 128 + h * 64 + (wave & 3) * 16 + sr;
+    const int gw = n0 + (wave >> 1) * 64 + h * 32 + (wave & 1) * 16 + sr;
+    xoff[h] = gx < RX ? ((unsigned)gx * (unsigned)ldx + (unsigned)(sc * 8)) * 2u : (unsigned)OOB;
+    woff[h] = gw < RW ? ((unsigned)gw * (unsigned)ldw + (unsigned)(sc * 8)) * 2u : (unsigned)OOB;
+  }
+  const int klim = kend - sc * 8;                        // chunk in range <=> its first k < klim
+  char* const sdst = smem + wave * 2048;
+  // one half-tile of K-tile `t` (k0 = kbeg + 64 t) into `slot` (buffer (t & 1) * BUF + SLOT_*); rows out of range carry OOB already
+  auto stage = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned roff, int slot, int t) {
+    const int k0 = kbeg + t * 64;
+    const unsigned v0 = k0 < klim ? roff + (unsigned)k0 * 2u : (unsigned)OOB;
+    const unsigned v1 = k0 + 32 < klim ? roff + (unsigned)(k0 + 32) * 2u : (unsigned)OOB;
+    char* d = sdst + slot;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(d), 16, (int)v0, 0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(d + 1024), 16, (int)v1, 0, 0, 0);
+  };
+  // ---- fragment reads: lane l <- row (l & 15), chunk (l >> 4) of the subtile, swizzled
+  const int fro = (lane & 15) * 64 + (((lane >> 4) ^ (((lane >> 3) & 1) << 1)) << 4);
+  const char* const xrd = smem + fro + wm * 8192;       // + buffer + slot + a' * 2048 + kk * 1024
+  const char* const wrd = smem + fro + wn * 4096;       // + buffer + slot + b' * 2048 + kk * 1024
+
+  // prologue: 7 half-tiles (tile 0, and W0 X0 W1 of tile 1); tile 0 landed
+  stage(ws, woff[0], SLOT_W0, 0); stage(xs, xoff[0], SLOT_X0, 0); stage(ws, woff[1], SLOT_W1, 0); stage(xs, xoff[1], SLOT_X1, 0);
+  stage(ws, woff[0], BUF + SLOT_W0, 1); stage(xs, xoff[0], BUF + SLOT_X0, 1); stage(ws, woff[1], BUF + SLOT_W1, 1);
+  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  const bool grp_b = wave >= 4;
+  if (grp_b) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
+
+  bf16x8 xf[4][2], w0[2][2], w1[2][2];
+#define VAC_P8_BAR()  __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0)
+#define VAC_P8_MFMA(A0, B0, WF)                                                                                          \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                     \
+  __builtin_amdgcn_sched_barrier(0);                                                                                     \
+  __builtin_amdgcn_s_setprio(1);                                                                                         \
+  _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                                       \
+    _Pragma("unroll") for (int b = 0; b < 2; ++b)                                                                        \
+      _Pragma("unroll") for (int a = 0; a < 4; ++a)                                                                      \
+        acc[B0 + b][A0 + a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WF[b][kk], xf[a][kk], acc[B0 + b][A0 + a], 0, 0, 0); \
+  __builtin_amdgcn_s_setprio(0);                                                                                         \
+  VAC_P8_BAR()
+  // the four phases of K-tile t, which lives in buffer PAR = t & 1
+  auto ktile = [&](auto par_c, int t) {
+    constexpr int PAR = decltype(par_c)::value;
+    const char* const xb = xrd + PAR * BUF;
+    const char* const wb = wrd + PAR * BUF;
+    // phase 1
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) w0[b][kk] = *(const bf16x8*)(wb + SLOT_W0 + b * 2048 + kk * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) xf[a][kk] = *(const bf16x8*)(xb + SLOT_X0 + a * 2048 + kk * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+    stage(xs, xoff[1], (PAR ^ 1) * BUF + SLOT_X1, t + 1);
+    asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");   // the W0 reads: their slot is restaged in phase 2
+    VAC_P8_BAR();
+    VAC_P8_MFMA(0, 0, w0);
+    // phase 2
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) w1[b][kk] = *(const bf16x8*)(wb + SLOT_W1 + b * 2048 + kk * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+    stage(ws, woff[0], PAR * BUF + SLOT_W0, t + 2);
+    VAC_P8_BAR();
+    VAC_P8_MFMA(0, 2, w1);
+    // phase 3
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) xf[a][kk] = *(const bf16x8*)(xb + SLOT_X1 + a * 2048 + kk * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+    stage(xs, xoff[0], PAR * BUF + SLOT_X0, t + 2);
+    VAC_P8_BAR();
+    VAC_P8_MFMA(4, 2, w1);
+    // phase 4: all of tile t+1 has landed (this wave's pieces) once only tile t+2's three half-tiles are in flight
+    stage(ws, woff[1], PAR * BUF + SLOT_W1, t + 2);
+    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    VAC_P8_BAR();
+    VAC_P8_MFMA(4, 0, w0);
+  };
+  for (int t = 0; t < ntile; t += 2) {
+    ktile(IC<0>{}, t);
+    if (t + 1 >= ntile) break;
+    ktile(IC<1>{}, t + 1);
+  }
+#undef VAC_P8_MFMA
+#undef VAC_P8_BAR
+  if (!grp_b) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
+}
+
 // DR: compile the activation-dropout epilogues (GemmP::drop_*) — their own instantiations (gemm_t*d.hip) for the same reason as CE:
 // inside the general kernels the extra epilogue code cost the 128 x 128 tile 18 VGPRs (occupancy 3 -> 2) and the 256 x 256 tile
 // scratch.  A DR kernel always applies dropout (the host launches it only with drop_thr != 0).
@@ -257,7 +394,7 @@ __device__ __forceinline__ void wait_vm_lgkm() { asm volatile("s_waitcnt vmcnt(%
 // logits -> part_sum[m][tn] (p.out).  Backward: p.residual holds FOUR floats per row {lse, coef, coef * (1 - eps), coef * eps / V}.
 // One output tile: rows [m0, m0 + BM) x columns [n0, n0 + BN), reduction slice `zsplit`.  `tn` = this tile's column index inside
 // its row panel and p.tiles_n the number of tiles that share the panel (the xsum K-steps are dealt round-robin over them).
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false, bool LS = false>
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false, bool LS = false, bool P8 = false>
 __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const int n0, const int tn, const int zsplit, const int tile_id = 0) {
   constexpr int NWAVE = WM * WN, NTHR = 64 * NWAVE;
   constexpr int TM = BM / WM, TN = BN / WN;             // per-wave output sub-tile
@@ -319,17 +456,23 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   // all out-of-range -> zero fill, never read) so the counted vmcnt below is a compile-time constant.
   constexpr int LOADS = (BM + BN) * BKT * 2 / 1024 / NWAVE;   // LDS-DMA instructions per wave per K-tile
   static_assert(LOADS * (NSTAGE - 2) <= 63, "vmcnt immediate");
-  constexpr bool PIPED = PIPE && BKT == 64 && NSTAGE == 2;
+  constexpr bool PIPED = PIPE && BKT == 64 && NSTAGE == 2 && !P8;
   constexpr int PRO = PIPED ? 2 : NSTAGE - 1;            // tiles staged before the loop
+  if constexpr (!P8) {
 #pragma unroll
-  for (int s = 0; s < PRO; ++s) {
-    stage_tile<XKS, BM, BKT, NWAVE>(xs, smem + s * STAGE, m0, RX, kbeg + s * BKT, kend, p.ldx, wave, lane);
-    stage_tile<WKS, BN, BKT, NWAVE>(ws, smem + s * STAGE + XT, n0, RW, kbeg + s * BKT, kend, p.ldw, wave, lane);
+    for (int s = 0; s < PRO; ++s) {
+      stage_tile<XKS, BM, BKT, NWAVE>(xs, smem + s * STAGE, m0, RX, kbeg + s * BKT, kend, p.ldx, wave, lane);
+      stage_tile<WKS, BN, BKT, NWAVE>(ws, smem + s * STAGE + XT, n0, RW, kbeg + s * BKT, kend, p.ldw, wave, lane);
+    }
+    wait_vm_lgkm<LOADS * (PRO - 1)>();                   // tile 0 landed
+    __builtin_amdgcn_s_barrier();
   }
-  wait_vm_lgkm<LOADS * (PRO - 1)>();                     // tile 0 landed
-  __builtin_amdgcn_s_barrier();
   int cur = 0, nxt = NSTAGE - 1;
-  if constexpr (PIPE && BKT == 32 && NSTAGE == 4) {
+  if constexpr (P8) {
+    static_assert(BM == 256 && BN == 256 && WM == 2 && WN == 4 && BKT == 64 && NSTAGE == 2 && !XKS && !WKS,
+                  "8-phase loop: 256 x 256 tile, 2 x 4 waves, both operands K-contiguous");
+    p8_loop(acc, smem, xs, ws, m0, n0, RX, RW, kbeg, kend, ntile, p.ldx, p.ldw, wave, lane);
+  } else if constexpr (PIPE && BKT == 32 && NSTAGE == 4) {
     // Ping-pong K loop (8 waves, two per SIMD; 32-wide K stages in a 4-slot ring).  The waves of a workgroup form two
     // groups, A = waves 0..3 and B = waves 4..7 (SIMD partners), that run the same sequence one interval apart:
     //     A:  MEM(0) | COMP(0) | MEM(1) | COMP(1) | ...
@@ -924,7 +1067,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
 }
 
 
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE = false, bool DR = false>
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE = false, bool DR = false, bool P8 = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
   if (p.debug & 8) return;
   // XCD-aware work order.  Workgroup L of the 1-D grid runs on XCD L % 8, each with its own 4 MiB L2.
@@ -944,7 +1087,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
   }
   const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
-  gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XKS, WKS, CE, DR>(p, tm * BM, tn * BN, tn, zsplit, bid);
+  gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XKS, WKS, CE, DR, false, P8>(p, tm * BM, tn * BN, tn, zsplit, bid);
 }
 
 // The cross-entropy kernel with the label-smoothing epilogues (forward layout, no split-K): the same tile walk as gemm_kernel.
@@ -1036,7 +1179,7 @@ int launch_gemm_group(const GroupP& g, hipStream_t s) {
 }
 
 
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE = false, bool CE = false, bool DR = false>
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE = false, bool CE = false, bool DR = false, bool P8 = false>
 int launch_gemm(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
   GemmP p = p0;
   p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
@@ -1046,14 +1189,17 @@ int launch_gemm(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s)
   static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
 #define VAC_LAUNCH(XK, WK)                                                                            \
   do {                                                                                                \
-    auto kern = gemm_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XK, WK, CE, DR>;                                          \
+    auto kern = gemm_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XK, WK, CE, DR, P8>;                                      \
     if (lds > 65536) {                                                                                \
       static bool once = false;                                                                       \
       if (!once) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; } \
     }                                                                                                 \
     hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                                 \
   } while (0)
-  if constexpr (CE) {
+  if constexpr (P8) {
+    if (xks || wks) { vacnic_set_error("gemm: the 8-phase loop is built for the forward layout (both operands K-contiguous)"); return VACNIC_UNSUPPORTED; }
+    VAC_LAUNCH(false, false);
+  } else if constexpr (CE) {
     if (xks || wks) { vacnic_set_error("gemm: the cross-entropy epilogues are built for the forward layout only"); return VACNIC_UNSUPPORTED; }
     VAC_LAUNCH(false, false);
   } else if constexpr (DR) {         // activation dropout: the forward Linear and the dgrad that carries act' (K-contiguous X)
@@ -1073,6 +1219,7 @@ int launch_gemm(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s)
 
 // one entry per tile configuration (defined in gemm_t*.hip)
 int launch_t256(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);   // 256x256 ping-pong
+int launch_t258(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);   // 256x256 8-phase counted-wait loop (forward layout)
 int launch_t264(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);   // 256x128 ping-pong
 int launch_t128(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);   // 128x128 software-pipelined
 int launch_t64(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);    // 64x128, 4-deep ring
