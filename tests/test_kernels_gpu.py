@@ -75,6 +75,24 @@ def test_gemm_padded_ldo_and_f32_out(K):
     close(o32, ref, 1e-4, 1e-4, "f32 out")
 
 
+@pytest.mark.parametrize("hint", [256, 264])
+def test_gemm_f32_out_unaligned_rows_256_row_tiles(K, hint):
+    """fp32 store and fp32 accumulate on a 256-row tile whose output rows are neither 16-byte aligned (ldo % 4 != 0) nor a multiple
+    of 8 wide: every chunk goes element by element through epilogue8, the last one of a row ragged, with a bias.  One tile plus
+    a ragged edge in both directions."""
+    M, N, K_ = 260, 261, 72
+    x = rnd(M, K_, seed=1); w = rnd(N, K_, scale=0.05, seed=2); b = rnd(N, dtype=torch.float32, seed=3)
+    ref = x.float() @ w.float().t() + b
+    ld = 263
+    out = torch.full((M, ld), 7.0, device="cuda")
+    K.gemm(x, w, M, N, K_, bias=b, out=out, ldo=ld, out_mode=1, tile_hint=hint)
+    close(out[:, :N], ref, 1e-4, 1e-4, f"f32 store, ldo {ld}, hint {hint}")
+    assert (out[:, N:] == 7.0).all(), "columns >= N must not be written"
+    K.gemm(x, w, M, N, K_, bias=b, out=out, ldo=ld, out_mode=2, tile_hint=hint)
+    close(out[:, :N], 2 * ref, 1e-4, 1e-4, f"f32 accumulate, ldo {ld}, hint {hint}")
+    assert (out[:, N:] == 7.0).all(), "columns >= N must not be written"
+
+
 @pytest.mark.parametrize("act", ["gelu", "tanh", "quick_gelu"])
 def test_gemm_epilogues(K, act):
     M, N, K_ = 200, 264, 128

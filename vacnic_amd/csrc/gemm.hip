@@ -30,6 +30,25 @@ using namespace vacgemm;
 
 namespace {
 
+// Wave reduction of 32 partial sums per lane (the M x CW dot products of the skinny kernels), shared by both of them: a
+// reduce-scatter butterfly — at offset 32,16,8,4,2 every lane hands the half of its values its partner keeps and adds the half it
+// keeps (16+8+4+2+1 exchanges), then one last exchange at offset 1 -> 32 cross-lane moves for 32 sums instead of 192.  Declares
+// `float V` = sum number `IDX` (= m * CW + c), which the lane pair (LANE, LANE ^ 1) holds; the even lane writes it.
+// (A macro on purpose: as an inlined function the same statements were allocated 104 instead of 90 registers in gemm_skinny_kernel.)
+#define VAC_BFLY(ACC, LANE, OFF, HALF)                                                 \
+  {                                                                              \
+    const bool up = ((LANE) & OFF) != 0;                                           \
+    _Pragma("unroll") for (int i = 0; i < HALF; ++i) {                           \
+      const float send = up ? ACC[i] : ACC[HALF + i];                            \
+      const float keep = up ? ACC[HALF + i] : ACC[i];                            \
+      ACC[i] = keep + __shfl_xor(send, OFF, 64);                                 \
+    }                                                                            \
+  }
+#define VAC_BFLY32(ACC, LANE, V, IDX)                                                                                     \
+  VAC_BFLY(ACC, LANE, 32, 16) VAC_BFLY(ACC, LANE, 16, 8) VAC_BFLY(ACC, LANE, 8, 4) VAC_BFLY(ACC, LANE, 4, 2) VAC_BFLY(ACC, LANE, 2, 1) \
+  float V = ACC[0] + __shfl_xor(ACC[0], 1, 64);                                                                       \
+  const int IDX = ((((LANE) >> 5) & 1) << 4) | ((((LANE) >> 4) & 1) << 3) | ((((LANE) >> 3) & 1) << 2) | ((((LANE) >> 2) & 1) << 1) | (((LANE) >> 1) & 1);
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Skinny-M GEMM (M <= 8): the single-token decoder of caption generation (MFULL:474-501, beams*batch rows) and any other
 // GEMM whose X is a handful of rows.  HBM-bound: W [N,K] is streamed exactly once; X (<= 8 x K bf16) is re-read from
@@ -42,7 +61,8 @@ __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmP p) {
   const int lane = threadIdx.x & 63;
   const int kw = KW == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int n0 = blockIdx.x * CW;
-  constexpr int NV = MR * CW;                        // 32 partial dot products per lane
+  constexpr int NV = MR * CW;                        // 32 partial dot products per lane (VAC_BFLY32)
+  static_assert(NV == 32, "butterfly written for 32 values per lane");
   float acc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.f;
@@ -70,22 +90,7 @@ __global__ __launch_bounds__(64 * KW) void gemm_skinny_kernel(GemmP p) {
       }
     }
   }
-  // reduce-scatter butterfly: at offset 32,16,8,4,2 every lane hands the half of its values its partner keeps and adds the
-  // half it keeps (16+8+4+2+1 exchanges), then one last exchange at offset 1 -> 32 cross-lane moves for 32 sums instead of 192.
-  static_assert(NV == 32, "butterfly written for 32 values per lane");
-#define VAC_BFLY(OFF, HALF)                                                      \
-  {                                                                              \
-    const bool up = (lane & OFF) != 0;                                           \
-    _Pragma("unroll") for (int i = 0; i < HALF; ++i) {                           \
-      const float send = up ? acc[i] : acc[HALF + i];                            \
-      const float keep = up ? acc[HALF + i] : acc[i];                            \
-      acc[i] = keep + __shfl_xor(send, OFF, 64);                                 \
-    }                                                                            \
-  }
-  VAC_BFLY(32, 16) VAC_BFLY(16, 8) VAC_BFLY(8, 4) VAC_BFLY(4, 2) VAC_BFLY(2, 1)
-#undef VAC_BFLY
-  float v = acc[0] + __shfl_xor(acc[0], 1, 64);
-  const int idx = (((lane >> 5) & 1) << 4) | (((lane >> 4) & 1) << 3) | (((lane >> 3) & 1) << 2) | (((lane >> 2) & 1) << 1) | ((lane >> 1) & 1);
+  VAC_BFLY32(acc, lane, v, idx)
   if constexpr (KW > 1) {
     __shared__ float part[KW][NV];
     if ((lane & 1) == 0) part[kw][idx] = v;
@@ -214,6 +219,7 @@ __global__ __launch_bounds__(64) void gemv_ln_kernel(GemvLnP p) {
   }
   // 3. dot products + the skinny kernel's reduce-scatter butterfly and epilogue
   constexpr int NV = MR * CW;
+  static_assert(NV == 32, "butterfly written for 32 values per lane");
   float acc[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) acc[i] = 0.f;
@@ -228,20 +234,7 @@ __global__ __launch_bounds__(64) void gemv_ln_kernel(GemvLnP p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[m * CW + c] += h[m][i][j] * wv[j];
     }
-  static_assert(NV == 32, "butterfly written for 32 values per lane");
-#define VAC_BFLY(OFF, HALF)                                                      \
-  {                                                                              \
-    const bool up = (lane & OFF) != 0;                                           \
-    _Pragma("unroll") for (int i = 0; i < HALF; ++i) {                           \
-      const float send = up ? acc[i] : acc[HALF + i];                            \
-      const float keep = up ? acc[HALF + i] : acc[i];                            \
-      acc[i] = keep + __shfl_xor(send, OFF, 64);                                 \
-    }                                                                            \
-  }
-  VAC_BFLY(32, 16) VAC_BFLY(16, 8) VAC_BFLY(8, 4) VAC_BFLY(4, 2) VAC_BFLY(2, 1)
-#undef VAC_BFLY
-  float v = acc[0] + __shfl_xor(acc[0], 1, 64);
-  const int idx = (((lane >> 5) & 1) << 4) | (((lane >> 4) & 1) << 3) | (((lane >> 3) & 1) << 2) | (((lane >> 2) & 1) << 1) | ((lane >> 1) & 1);
+  VAC_BFLY32(acc, lane, v, idx)
   if ((lane & 1) == 0) {
     const int m = idx / CW, c = idx % CW;
     const int n = n0 + c;
@@ -254,6 +247,9 @@ __global__ __launch_bounds__(64) void gemv_ln_kernel(GemvLnP p) {
     }
   }
 }
+
+#undef VAC_BFLY32
+#undef VAC_BFLY
 
 }  // namespace
 
@@ -298,6 +294,14 @@ static double cfg_cost(const TileCfg& c, int64_t M, int64_t N, int64_t kper, int
 }
 
 static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0, bool ce_smooth = false);
+
+// A/B aid for whole-step measurements on ONE box (device-to-device spread is larger than most kernel deltas):
+// VACNIC_GEMM_DEBUG=<bits> is OR-ed into GemmP::debug of every launch (gemm_kernel.h: e.g. 16 = EPI_F32_STAGED everywhere)
+static int gemm_env_debug() {
+  static int env_debug = -1;
+  if (env_debug < 0) { const char* e = getenv("VACNIC_GEMM_DEBUG"); env_debug = e ? atoi(e) : 0; }
+  return env_debug;
+}
 
 // fix-up buffers: partial tiles are padded to whole tiles; the bound covers every configuration (64-row tiles pad M the least,
 // 256 x 256 the most), so the caller need not know which one a launch picks
@@ -430,18 +434,11 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
     return VACNIC_OK;
   }
   const int force = tile_hint % 1000;
-  p.debug = tile_hint / 1000;
-  {
-    // A/B aid for whole-step measurements on ONE box (device-to-device spread is larger than most kernel deltas):
-    // VACNIC_GEMM_DEBUG=<bits> is OR-ed into the debug mask of every launch (e.g. 80 = fp32 epilogue + one workgroup per tile)
-    static int env_debug = -1;
-    if (env_debug < 0) { const char* e = getenv("VACNIC_GEMM_DEBUG"); env_debug = e ? atoi(e) : 0; }
-    p.debug |= env_debug;
-  }
-  // the bf16 epilogue addresses its outputs through 32-bit buffer offsets: larger outputs take the fp32-staged path
-  if (((a->M - 1) * a->ldo + a->N) * 2 >= 0x7ffffff0LL) p.debug |= 16;
-  if ((a->preact != nullptr) + (a->dact_src != nullptr) + (a->residual != nullptr) > 1) p.debug |= 16;   // bf16 epilogue: one extra operand
-  if (p.drop_thr && !a->preact && !a->dact_src) p.debug |= 16;     // dropout rides on the saved-pre-activation / act' instances of the bf16 epilogue
+  p.debug = tile_hint / 1000 | gemm_env_debug();
+  // dispatch of the epilogue (256-row tiles): what the bf16 transposed epilogue cannot serve takes the fp32 staged one
+  if (((a->M - 1) * a->ldo + a->N) * 2 >= 0x7ffffff0LL) p.debug |= EPI_F32_STAGED;      // it addresses its outputs through 32-bit buffer offsets
+  if ((a->preact != nullptr) + (a->dact_src != nullptr) + (a->residual != nullptr) > 1) p.debug |= EPI_F32_STAGED;   // it carries one extra operand
+  if (p.drop_thr && !a->preact && !a->dact_src) p.debug |= EPI_F32_STAGED;     // dropout rides on its saved-pre-activation / act' instances
   const bool big = force == 256;
   const bool mid = force == 128;
   if (p.drop_thr) {                 // activation dropout: 256 x 256, 256 x 128 and 64 x 128 tiles carry the DR epilogues
@@ -475,12 +472,7 @@ extern "C" int vacnic_wgrad_group(const vacnic_wgrad_job* jobs, int64_t njobs, v
   constexpr int64_t US = (int64_t)GROUP_UT * 128;
   GroupP g;
   g.nunits = 0;
-  g.debug = 0;
-  {
-    static int env_debug = -1;
-    if (env_debug < 0) { const char* e = getenv("VACNIC_GEMM_DEBUG"); env_debug = e ? atoi(e) : 0; }
-    g.debug = env_debug & ~8;
-  }
+  g.debug = gemm_env_debug() & ~DBG_RETURN;
   auto flush = [&]() -> int {
     if (g.nunits == 0) return VACNIC_OK;
     int kmax = 0;
@@ -638,21 +630,17 @@ extern "C" int vacnic_lmhead_ce_fwd(const vacnic_lmhead_ce_args* a, void* stream
     vacnic_set_error("lmhead_ce_fwd: part_tiles must equal ceil(V / 256) = %ld", (long)tiles);
     return VACNIC_BAD_SHAPE;
   }
-  if (smooth) {
-    g.out = a->part_sum;                 // the label-smoothing epilogue writes the per-tile logit sums through `out`
-    if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0, true)) return e;
-    hipLaunchKernelGGL(ce_combine_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part, a->tl, a->targets, a->row_lse,
-                       a->loss_sum, a->count, (int)a->R, (int)tiles, a->ignore_index);
-    VLAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_smooth_term_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part_sum, a->tl, a->targets,
-                       a->loss_sum, (int)a->R, (int)tiles, a->ignore_index, a->label_smoothing, 1.f / (float)a->V);
-    VLAUNCH_CHECK();
-    return VACNIC_OK;
-  }
-  if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0)) return e;
-  hipLaunchKernelGGL(ce_combine_kernel, dim3((unsigned)((a->R + 3) / 4)), dim3(256), 0, st, a->part, a->tl, a->targets, a->row_lse,
+  if (smooth) g.out = a->part_sum;       // the label-smoothing epilogue writes the per-tile logit sums through `out`
+  if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0, smooth)) return e;
+  const dim3 rows4((unsigned)((a->R + 3) / 4));
+  hipLaunchKernelGGL(ce_combine_kernel, rows4, dim3(256), 0, st, a->part, a->tl, a->targets, a->row_lse,
                      a->loss_sum, a->count, (int)a->R, (int)tiles, a->ignore_index);
   VLAUNCH_CHECK();
+  if (smooth) {
+    hipLaunchKernelGGL(ce_smooth_term_kernel, rows4, dim3(256), 0, st, a->part_sum, a->tl, a->targets,
+                       a->loss_sum, (int)a->R, (int)tiles, a->ignore_index, a->label_smoothing, 1.f / (float)a->V);
+    VLAUNCH_CHECK();
+  }
   return VACNIC_OK;
 }
 

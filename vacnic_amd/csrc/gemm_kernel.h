@@ -27,7 +27,22 @@ struct GemmP {
   unsigned drop_thr; float drop_inv; unsigned long long drop_seed; const unsigned long long* drop_seed_dev;
   float* ws;            // split-K with ordered fix-up (see gemm_tile): fp32 partial tiles [tile][split][BM*BN]; nullptr = atomics
   unsigned* cnt;        // one arrival counter per output tile (zero before the launch, zero again after it)
-  int debug;            // profiling aid (tile_hint >= 1000): bit0 skip the global stores, bit1 skip the K loop, bit2 skip the epilogue, bit3 return at once, bit4 fp32 staged epilogue, bit5 no LDS-DMA in the loop, bit7 no fragment reads
+  int debug;            // DBG_* / EPI_F32_STAGED bits below (tile_hint / 1000, OR-ed with VACNIC_GEMM_DEBUG)
+};
+
+// Bits of GemmP::debug.  EPI_F32_STAGED is ordinary dispatch: "take the fp32 staged epilogue, not the bf16 transposed one".  The
+// host sets it for launches the bf16 epilogue cannot serve (gemm.hip: gemm_one), and an A/B run may force it.  The DBG_* bits
+// are profiling aids (time one part of the kernel by leaving another out; results are then wrong): no production launch sets them.
+enum : int {
+  DBG_NO_STORE = 1,         // skip the global stores of the epilogue
+  DBG_NO_KLOOP = 2,         // skip the K loop (ntile = 0)
+  DBG_NO_EPILOGUE = 4,      // return after the K loop
+  DBG_RETURN = 8,           // return at once (launch overhead)
+  EPI_F32_STAGED = 16,      // fp32 staged epilogue (dispatch, see above)
+  DBG_NO_DMA = 32,          // no LDS-DMA inside the loop (ping-pong and ring loops)
+  DBG_NO_MATH = 64,         // ring loop: neither fragment reads nor MFMAs
+  DBG_NO_FRAG_READS = 128,  // fragment reads in the first iteration only (ping-pong and ring loops)
+  DBG_OLD_PASS_MAP = 256,   // fp32 staged epilogue: one wave row-group per pass (the previous mapping)
 };
 
 // f(k) of the K-strided swizzle: distinct for the 8 k-rows one tr-read half touches.
@@ -103,18 +118,13 @@ __device__ __forceinline__ bf16x8 read_frag(const char* lds_tile, int rbase, int
 // Epilogue on 8 consecutive outputs of one row (read back from the LDS-staged C tile): bias, saved
 // pre-activation, activation or fused activation-backward, residual, then a 16-byte (bf16) /
 // 2x16-byte (f32) store or 8 f32 atomics on 32 contiguous bytes.
-__device__ __forceinline__ void load8bf(const bf16_t* p, float v[8]) {
-  u32x4 r = *(const u32x4*)p;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
-}
-__device__ __forceinline__ void store8bf(bf16_t* p, const float v[8]) {
-  *(u32x4*)p = (u32x4){pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
-}
-
 __device__ __forceinline__ void unpack8bf(u32x4 r, float v[8]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) { v[2 * i] = __uint_as_float(r[i] << 16); v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u); }
+}
+__device__ __forceinline__ void load8bf(const bf16_t* p, float v[8]) { unpack8bf(*(const u32x4*)p, v); }
+__device__ __forceinline__ void store8bf(bf16_t* p, const float v[8]) {
+  *(u32x4*)p = (u32x4){pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
 }
 
 // 8 consecutive, fully in-range, 16-byte-aligned outputs of one row.  Bias and the raw residual / activation-source words
@@ -150,7 +160,7 @@ __device__ __forceinline__ void epilogue8_vec(const GemmP& p, float v[8], size_t
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] += d[j];
   }
-  if (p.debug & 1) {
+  if (p.debug & DBG_NO_STORE) {
     if (v[0] == 12345.678f) ((bf16_t*)p.out)[off] = 0;
   } else if (p.out_mode == 0) {
     store8bf((bf16_t*)p.out + off, v);
@@ -205,7 +215,7 @@ __device__ __forceinline__ void epilogue8(const GemmP& p, float v[8], int m, int
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] += d[j];
   }
-  if (p.debug & 1) {
+  if (p.debug & DBG_NO_STORE) {
     if (v[0] == 12345.678f) ((bf16_t*)p.out)[off] = 0;      // keeps the values live, never true in practice
   } else if (p.out_mode == 0) {
     bf16_t* o = (bf16_t*)p.out + off;
@@ -407,7 +417,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   const int wm = wave % WM, wn = wave / WM;
   const int kbeg = zsplit * p.k_per_split;
   const int kend = min(p.K, kbeg + p.k_per_split);
-  const int ntile = (p.debug & 2) ? 0 : (kend - kbeg + BKT - 1) / BKT;
+  const int ntile = (p.debug & DBG_NO_KLOOP) ? 0 : (kend - kbeg + BKT - 1) / BKT;
 
   __amdgpu_buffer_rsrc_t xs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
   __amdgpu_buffer_rsrc_t ws = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
@@ -496,13 +506,13 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
     for (int h = 0; h < nst; ++h) {
       const char* xr = smem + rd * STAGE;
       char* xw = smem + wr * STAGE;
-      if (!(p.debug & 128) || h == 0) {
+      if (!(p.debug & DBG_NO_FRAG_READS) || h == 0) {
 #pragma unroll
         for (int a = 0; a < FA; ++a) xf[a] = read_frag<XKS, BM, BKT>(xr, wm * TM + a * 16, 0, lane);
 #pragma unroll
         for (int b = 0; b < FB; ++b) wf[b] = read_frag<WKS, BN, BKT>(xr + XT, wn * TN + b * 16, 0, lane);
       }
-      if (!(p.debug & 32)) {
+      if (!(p.debug & DBG_NO_DMA)) {
         stage_tile<XKS, BM, BKT, NWAVE>(xs, xw, m0, RX, kbeg + (h + 3) * BKT, kend, p.ldx, wave, lane);
         stage_tile<WKS, BN, BKT, NWAVE>(ws, xw + XT, n0, RW, kbeg + (h + 3) * BKT, kend, p.ldw, wave, lane);
       }
@@ -578,16 +588,16 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   for (int t = 0; t < ntile; ++t) {
     char* xcur = smem + cur * STAGE;
     char* wcur = xcur + XT;
-    if (!(p.debug & 32)) {
+    if (!(p.debug & DBG_NO_DMA)) {
       // ring slot `nxt` was last read in iteration t-1 and every wave has passed that iteration's barrier
       char* xnext = smem + nxt * STAGE;
       stage_tile<XKS, BM, BKT, NWAVE>(xs, xnext, m0, RX, kbeg + (t + NSTAGE - 1) * BKT, kend, p.ldx, wave, lane);
       stage_tile<WKS, BN, BKT, NWAVE>(ws, xnext + XT, n0, RW, kbeg + (t + NSTAGE - 1) * BKT, kend, p.ldw, wave, lane);
     }
-    if (!(p.debug & 64))
+    if (!(p.debug & DBG_NO_MATH))
 #pragma unroll
     for (int kk = 0; kk < BKT / 32; ++kk) {
-      if (!(p.debug & 128) || t == 0) {
+      if (!(p.debug & DBG_NO_FRAG_READS) || t == 0) {
 #pragma unroll
         for (int a = 0; a < FA; ++a) xf[a] = read_frag<XKS, BM, BKT>(xcur, wm * TM + a * 16, kk, lane);
 #pragma unroll
@@ -621,7 +631,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
     }
   }
 
-  if (p.debug & 4) { if (acc[0][0][0] == 12345.678f) ((float*)p.out)[0] = 0.f; return; }
+  if (p.debug & DBG_NO_EPILOGUE) { if (acc[0][0][0] == 12345.678f) ((float*)p.out)[0] = 0.f; return; }
   // ---- split-K with an ORDERED FIX-UP instead of atomics (p.ws != nullptr): every K-slice workgroup of a tile deposits its fp32
   // partial tile in the workspace and takes a ticket; the LAST one to arrive sums all slices in slice order 0 .. S-1 — a fixed
   // order whoever comes last, so the result is bitwise reproducible — and runs the ordinary epilogue ONCE (bias, activation,
@@ -674,7 +684,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   // ---- direct epilogue for the common plain case (bf16 out, bias + activation only): each lane owns 4 consecutive n of
   // one m per accumulator tile -> bias as one 16-byte load, pack with v_cvt_pk_bf16_f32, one 8-byte store.  No LDS
   // round trip, no barriers; the 32-byte row pieces of the four n-groups are merged by the L2.
-  if (BM <= 128 && p.out_mode == 0 && !p.preact && !p.dact_src && !p.residual && (p.ldo & 3) == 0 && !(p.debug & 16) && !DR) {
+  if (BM <= 128 && p.out_mode == 0 && !p.preact && !p.dact_src && !p.residual && (p.ldo & 3) == 0 && !(p.debug & EPI_F32_STAGED) && !DR) {
     const int lm_ = lane & 15, ln4_ = (lane >> 4) * 4;
     const bool add_bias_ = p.bias != nullptr;
 #pragma unroll
@@ -716,7 +726,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   // pre-activation, fused activation-backward and residual are applied on the bf16 value after the transposition — the
   // arithmetic of a bf16 autocast Linear followed by a bf16 elementwise op.
   if constexpr (BM == 256 && BN >= 128) {
-    if (p.out_mode == 0 && (p.ldo & 7) == 0 && (p.N & 7) == 0 && !(p.debug & 16)) {
+    if (p.out_mode == 0 && (p.ldo & 7) == 0 && (p.N & 7) == 0 && !(p.debug & EPI_F32_STAGED)) {
       static_assert(BM * ROWB <= NSTAGE * STAGE, "bf16 C tile must fit in the operand ring");
       const bool act_in_regs = p.act != VACNIC_ACT_NONE && !p.preact && !p.dact_src;
       f32x4 bia[FB];
@@ -766,14 +776,14 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
         const int row = rb + k * RSTEP;
         cv[k] = *(const u32x4*)(smem + row * ROWB + ((c ^ (row & 15)) << 4));
       }
-      // Global traffic of the epilogue through buffer instructions: rows >= M (and, with debug bit 0, everything) fall
+      // Global traffic of the epilogue through buffer instructions: rows >= M (and, with DBG_NO_STORE, everything) fall
       // outside the descriptor's range — loads return 0, stores are dropped — so there is no branch around any access
       // (a branch per load makes hipcc wait for each load separately) and every wave issues exactly NIT stores per output.
       const unsigned span = (unsigned)((((size_t)p.M - 1) * p.ldo + p.N) * 2);
       const int n = n0 + c * 8;
       const unsigned rstride = (unsigned)(RSTEP * p.ldo * 2);
-      unsigned voff = (n + 8 <= p.N && !(p.debug & 1)) ? (unsigned)(((size_t)(m0 + rb) * p.ldo + n) * 2) : (unsigned)OOB;
-      const unsigned vstep = (n + 8 <= p.N && !(p.debug & 1)) ? rstride : 0u;
+      unsigned voff = (n + 8 <= p.N && !(p.debug & DBG_NO_STORE)) ? (unsigned)(((size_t)(m0 + rb) * p.ldo + n) * 2) : (unsigned)OOB;
+      const unsigned vstep = (n + 8 <= p.N && !(p.debug & DBG_NO_STORE)) ? rstride : 0u;
       __amdgpu_buffer_rsrc_t so = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, span, 0x00020000);
       const bool plain = !p.preact && !p.dact_src && !p.residual;
       // activation dropout (host: contiguous output, N % 16 == 0, never on the plain path): Philox block of this thread's column
@@ -862,7 +872,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
   // LDS row r of pass p holds tile row (r / RPWM) * TM + p * RPWM + r % RPWM.
   constexpr int RPWM = 64 / WM;
   static_assert((RPWM % 16 == 0 && TM % RPWM == 0) || BM < 64, "epilogue pass mapping");
-  const bool old_map = (p.debug & 256) != 0;      // A/B: one wave row-group per pass (the previous mapping)
+  const bool old_map = (p.debug & DBG_OLD_PASS_MAP) != 0;      // A/B: one wave row-group per pass (the previous mapping)
   auto tile_row = [&](int pass, int r) { return old_map ? pass * 64 + r : (r / RPWM) * TM + pass * RPWM + r % RPWM; };
 #pragma unroll
   for (int pass = 0; pass < PASSES; ++pass) {
@@ -1069,7 +1079,7 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
 
 template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE = false, bool DR = false, bool P8 = false>
 __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
-  if (p.debug & 8) return;
+  if (p.debug & DBG_RETURN) return;
   // XCD-aware work order.  Workgroup L of the 1-D grid runs on XCD L % 8, each with its own 4 MiB L2.
   //  * split-K launches (weight gradients): split z = L % nsplit, so one XCD (or nsplit/8 .. 8/nsplit of them) owns a whole
   //    K-slice and every row of dY / X in it is fetched once — all tiles of a slice run concurrently on that XCD
@@ -1093,29 +1103,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_kernel(GemmP p) {
 // The cross-entropy kernel with the label-smoothing epilogues (forward layout, no split-K): the same tile walk as gemm_kernel.
 template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
 __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_ce_smooth_kernel(GemmP p) {
-  if (p.debug & 8) return;
+  if (p.debug & DBG_RETURN) return;
   const int nt = p.tiles_m * p.tiles_n;
   const int q = nt >> 3, r = nt & 7, xcd = blockIdx.x & 7;
   const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
   const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
   gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, false, false, true, false, true>(p, tm * BM, tn * BN, tn, 0, bid);
-}
-
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
-int launch_gemm_ce_smooth(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
-  if (xks || wks || zsplits != 1) { vacnic_set_error("gemm: the cross-entropy epilogues are built for the forward layout without split-K"); return VACNIC_UNSUPPORTED; }
-  GemmP p = p0;
-  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
-  static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
-  auto kern = gemm_ce_smooth_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>;
-  if (lds > 65536) {
-    static bool once = false;
-    if (!once) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; }
-  }
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), lds, s, p);
-  VLAUNCH_CHECK();
-  return VACNIC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1162,56 +1155,65 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_group_kernel(GroupP g) {
   gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, true, true, false>(p, m0, n0, tn, g.kphase);
 }
 
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
-int launch_gemm_group(const GroupP& g, hipStream_t s) {
-  static_assert(BM == 128 && BN == 128, "units are GROUP_UT x GROUP_UT tiles of 128 x 128");
-  const int rounds = (g.nunits + 7) / 8;
-  dim3 grid(rounds * 8 * GROUP_UT * GROUP_UT), block(64 * WM * WN);
-  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
-  auto kern = gemm_group_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>;
-  if (lds > 65536) {
+// Launch KERN with LDS bytes of dynamic LDS; above 64 KiB the kernel is told so once (one flag per kernel: KERN is a template argument).
+template <auto KERN, size_t LDS, class P>
+void launch_lds(dim3 grid, dim3 block, hipStream_t s, const P& p) {
+  if (LDS > 65536) {
     static bool once = false;
-    if (!once) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; }
+    if (!once) { (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); once = true; }
   }
-  hipLaunchKernelGGL(kern, grid, block, lds, s, g);
+  hipLaunchKernelGGL(KERN, grid, block, LDS, s, p);
+}
+
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+int launch_gemm_ce_smooth(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
+  if (xks || wks || zsplits != 1) { vacnic_set_error("gemm: the cross-entropy epilogues are built for the forward layout without split-K"); return VACNIC_UNSUPPORTED; }
+  GemmP p = p0;
+  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
+  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
+  static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
+  launch_lds<gemm_ce_smooth_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>, lds>(dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), s, p);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
 
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+int launch_gemm_group(const GroupP& g, hipStream_t s) {
+  static_assert(BM == 128 && BN == 128, "units are GROUP_UT x GROUP_UT tiles of 128 x 128");
+  const int rounds = (g.nunits + 7) / 8;
+  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
+  launch_lds<gemm_group_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>, lds>(dim3(rounds * 8 * GROUP_UT * GROUP_UT), dim3(64 * WM * WN), s, g);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
 
 template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE = false, bool CE = false, bool DR = false, bool P8 = false>
 int launch_gemm(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
   GemmP p = p0;
   p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
-  const int nwg = p.tiles_m * p.tiles_n * zsplits;
-  dim3 grid(nwg), block(64 * WM * WN);
+  const dim3 grid(p.tiles_m * p.tiles_n * zsplits), block(64 * WM * WN);
   constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
   static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
-#define VAC_LAUNCH(XK, WK)                                                                            \
-  do {                                                                                                \
-    auto kern = gemm_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE, XK, WK, CE, DR, P8>;                                      \
-    if (lds > 65536) {                                                                                \
-      static bool once = false;                                                                       \
-      if (!once) { (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); once = true; } \
-    }                                                                                                 \
-    hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                                 \
-  } while (0)
+  auto launch = [&](auto xk, auto wk) {
+    launch_lds<gemm_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE, decltype(xk)::value != 0, decltype(wk)::value != 0, CE, DR, P8>, lds>(grid, block, s, p);
+  };
+  constexpr IC<0> no{};
+  constexpr IC<1> yes{};
   if constexpr (P8) {
     if (xks || wks) { vacnic_set_error("gemm: the 8-phase loop is built for the forward layout (both operands K-contiguous)"); return VACNIC_UNSUPPORTED; }
-    VAC_LAUNCH(false, false);
+    launch(no, no);
   } else if constexpr (CE) {
     if (xks || wks) { vacnic_set_error("gemm: the cross-entropy epilogues are built for the forward layout only"); return VACNIC_UNSUPPORTED; }
-    VAC_LAUNCH(false, false);
+    launch(no, no);
   } else if constexpr (DR) {         // activation dropout: the forward Linear and the dgrad that carries act' (K-contiguous X)
     if (xks) { vacnic_set_error("gemm: fused activation dropout is built for K-contiguous X (forward / dgrad layouts)"); return VACNIC_UNSUPPORTED; }
-    if (wks) VAC_LAUNCH(false, true); else VAC_LAUNCH(false, false);
+    if (wks) launch(no, yes); else launch(no, no);
   } else {
-    if (!xks && !wks) VAC_LAUNCH(false, false);
-    else if (!xks && wks) VAC_LAUNCH(false, true);
-    else if (xks && wks) VAC_LAUNCH(true, true);
-    else VAC_LAUNCH(true, false);
+    if (!xks && !wks) launch(no, no);
+    else if (!xks && wks) launch(no, yes);
+    else if (xks && wks) launch(yes, yes);
+    else launch(yes, no);
   }
-#undef VAC_LAUNCH
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
