@@ -345,6 +345,37 @@ int vacnic_adamw(const vacnic_adamw_args* a, void* stream);
  * rewritten; pass `out` as vacnic_adamw_args.clip_coef and the scaling happens where AdamW reads g. */
 int vacnic_grad_clip_coef(const float* g, int64_t n, float grad_scale, float max_norm, float* partials,
                           float* out, void* stream);
+/*
+ * Parameter groups (torch.optim.AdamW(param_groups)): every arena element belongs to one SEGMENT, a contiguous element
+ * range with its own learning-rate multiple, weight decay and frozen flag.  The table is built once on the host
+ * (vacnic_amd.arena.group_table) and lives in device memory owned by the optimizer:
+ *   seg_start  int64 [nseg + 1]   ascending ABSOLUTE arena offsets, seg_start[0] = 0, seg_start[nseg] = arena size
+ *   seg        [nseg]             values of segment s = [seg_start[s], seg_start[s + 1])
+ *   first_seg  int32 [nblocks]    the segment that holds arena element 1024 * b: where a thread's forward walk starts
+ * A boundary may fall on any element; a 4-wide vector that straddles one is updated element by element.  The walk is clamped
+ * at nseg - 1 and the block index at nblocks - 1, so a malformed table gives wrong values, never an access outside it.
+ *   not frozen: the vacnic_adamw update with lr = hyper[0] * lr_scale and the segment's weight_decay (same arithmetic order)
+ *   frozen:     p, m, v and the bf16 shadow are not written; g is still zeroed when zero_grad (backward still accumulates)
+ * p, g, m, v, p_bf16 may point INTO the arena (a DDP bucket): elem_base is the arena offset of p[0].
+ */
+typedef struct { float lr_scale, weight_decay; int32_t frozen; int32_t reserved; } vacnic_adamw_seg;
+typedef struct {
+  float* p; float* g; float* m; float* v; void* p_bf16; const float* hyper;
+  int64_t n; float beta1, beta2, eps, grad_scale; int32_t zero_grad;
+  const float* clip_coef;
+  const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
+  int64_t nseg, nblocks, elem_base;
+} vacnic_adamw_groups_args;
+int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stream);
+/* vacnic_grad_clip_coef over the non-frozen elements only (clip_grad_norm_ sees no gradient for a parameter left out of the
+ * optimizer): same fixed grid, per-thread order and reduction tree, so with no frozen segment the result is bitwise that of
+ * vacnic_grad_clip_coef. */
+typedef struct {
+  const float* g; int64_t n; float grad_scale, max_norm; float* partials; float* out;
+  const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
+  int64_t nseg, nblocks, elem_base;
+} vacnic_grad_clip_groups_args;
+int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* a, void* stream);
 /* get_linear_schedule_with_warmup on device (TRAIN:99-107): hyper[0] <- base_lr*lambda(k), hyper[1] <- k+1
  * where k = hyper[1] on entry = optimizer steps already taken.  Also increments *rng_counter (the device-side
  * dropout counter, may be NULL).  Call once before vacnic_adamw. */

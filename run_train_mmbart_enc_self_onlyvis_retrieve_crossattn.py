@@ -24,6 +24,7 @@ parser.add_argument("--do_retrieval", action="store_true")        # TRAINV: retr
 parser.set_defaults(only_image=True, no_mapping=True, use_secla=False, plm_type="facebook/bart-base", clip_type="ViT-B/16")
 run = _full.run
 build_config = _full.build_config
+train_args = _full.train_args
 
 
 if __name__ == "__main__":

@@ -27,3 +27,45 @@ for _ in range(10):
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 10
 print(f"grad_clip_coef: {ms:.3f} ms = {n*4/ms/1e9:.2f} TB/s")
+
+# ---- parameter groups (vacnic_adamw_groups): the same arena through the grouped kernel, in the same process, rows alternating.
+# Yardstick: the ungrouped rows; margin: the spread between their own repeats.
+from vacnic_amd.arena import no_decay_spec, table_from_segments
+from vacnic_amd.config import bart_large_vit_l14
+from vacnic_amd.models.mmbart import BartForMultiModalGeneration
+cfg, _ = bart_large_vit_l14()
+with torch.device("meta"):                 # layout only: names, shapes and arena slots of the real model, no weights
+    net = BartForMultiModalGeneration(cfg, enc_fusion_layer=cfg.enc_fusion_layer, dim_common=cfg.dim_common, prompt_size=cfg.prompt_size)
+net.finalize("meta")
+spec = [{"match": "embed_positions", "frozen": True}] + no_decay_spec(net)
+full = net.arena.group_table(net.named_parameters(), spec, 0.01).segments()
+segs = [(s, lr, wd, fr) for s, _, lr, wd, fr in full if s < n]          # the model's arena is larger than the bench arena: its first n elements
+real = table_from_segments(n, segs).to("cuda")
+one = table_from_segments(n, [(0, 1.0, 0.01, False)]).to("cuda")
+print(f"BART-large VACNIC arena: {net.arena.n / 1e6:.0f}M elements, {len(full)} segments; bench table: {real.nseg} segments over the first "
+      f"{n / 1e6:.0f}M elements, {sum(fr for *_, fr in segs)} frozen")
+variants = [("ungrouped K.adamw", lambda: K.adamw(p, g, m, v, p16, hyper, n, zero_grad=True)),
+            ("grouped, 1 segment", lambda: K.adamw_groups(p, g, m, v, p16, hyper, n, one, zero_grad=True)),
+            (f"grouped, {real.nseg} segments", lambda: K.adamw_groups(p, g, m, v, p16, hyper, n, real, zero_grad=True)),
+            ("grad_clip_coef", lambda: K.grad_clip_coef(g, n, 0.1, out=out)),
+            (f"grad_clip_coef_groups, {real.nseg} segments", lambda: K.grad_clip_coef_groups(g, n, 0.1, real, out=out))]
+rows = {name: [] for name, _ in variants}
+for rep in range(3):
+    for name, fn in variants:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        rows[name].append(e0.elapsed_time(e1) / 10)
+        print(f"row {rep}: {name}: {rows[name][-1]:.3f} ms (10 launches)")
+for base, names in (("ungrouped K.adamw", [v[0] for v in variants[1:3]]), ("grad_clip_coef", [variants[4][0]])):
+    b = rows[base]
+    mean = sum(b) / len(b)
+    print(f"{base}: mean {mean:.3f} ms, spread of its own rows {max(b) - min(b):.3f} ms")
+    for name in names:
+        r = rows[name]
+        print(f"  {name}: mean {sum(r) / len(r):.3f} ms = {sum(r) / len(r) - mean:+.3f} ms against it (rows {', '.join(f'{x:.3f}' for x in r)})")

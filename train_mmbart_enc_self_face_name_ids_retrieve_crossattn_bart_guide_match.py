@@ -83,6 +83,12 @@ parser.add_argument("--resume", type=str, default="", help="checkpoint written b
 
 parser.add_argument("--label_smoothing", type=float, default=0.0, help="label smoothing of the training text loss, as torch's "
                     "CrossEntropyLoss(label_smoothing=) (0.1 in the usual BART fine-tuning recipe); the validation loss stays the plain NLL")
+# parameter groups of the optimizer (vacnic_amd.training.param_group_spec); all off by default = one group, as in the reference
+parser.add_argument("--no_decay_bias_ln", default=False, type=_b, help="no weight decay on biases and LayerNorm parameters")
+parser.add_argument("--lr_scale", action="append", default=[], metavar="REGEX=FLOAT", help="parameters whose name matches REGEX train at "
+                    "FLOAT times the scheduled learning rate, e.g. 'prompt_mlp|visual_map=10' (repeatable; the first match wins)")
+parser.add_argument("--freeze", action="append", default=[], metavar="REGEX", help="parameters whose name matches REGEX are not "
+                    "updated (repeatable); their gradients are still computed")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -105,13 +111,29 @@ def build_config(args):
     return cfg, ClipVisionConfig(**vkw)
 
 
+def train_args(args, total_steps):
+    """TrainArgs for the parsed flags."""
+    from vacnic_amd.training import TrainArgs
+    scales = []
+    for item in args.lr_scale:
+        rx, sep, val = item.rpartition("=")
+        if not sep or not rx:
+            raise ValueError(f"--lr_scale {item!r}: expected REGEX=FLOAT")
+        scales.append((rx, float(val)))
+    return TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
+                     num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
+                     mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
+                     no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
+                     no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze))
+
+
 def run(args, batches=None):
     import torch
     import torch.distributed as dist
     from vacnic_amd import ops, streams, synthetic
     from vacnic_amd.ddp import DistributedDataParallel
-    from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, TrainArgs, build_models, eval_epoch, gen_caption_from_loader_bart, to_device,
-                                     train_step)
+    from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, build_models, eval_epoch, gen_caption_from_loader_bart, param_group_spec,
+                                     to_device, train_step)
 
     if not args.no_clip_loss or not args.freeze_clip:
         raise NotImplementedError("CLIP contrastive loss / CLIP fine-tuning are out of scope (SURVEY §2 row 20): pass --no_clip_loss True --freeze_clip True")
@@ -143,13 +165,11 @@ def run(args, batches=None):
         if steps_per_epoch <= 0:
             raise ValueError("the training shard holds fewer samples than one global batch")
     total_steps = int(args.num_epoch) * steps_per_epoch          # TRAIN:99 (not divided by world size there either)
-    targs = TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
-                      num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
-                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
-                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm)
+    targs = train_args(args, total_steps)
     net = DistributedDataParallel(model, device_ids=[local], output_device=local) if world > 1 else model
     opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay, num_warmup_steps=args.warmup_rate * total_steps,
-                     num_training_steps=total_steps, world_size=world)
+                     num_training_steps=total_steps, world_size=world, param_groups=param_group_spec(model, targs),
+                     named_parameters=model.named_parameters())
     step, t0, hist = 0, time.time(), []
     plans = {}
     min_val_loss = 999.0                      # TRAIN:452

@@ -122,3 +122,181 @@ class ParamArena:
             out.append((start, end))
             end = start
         return out
+
+    def group_table(self, named_params, spec, default_wd):
+        """parameter-group table of this arena (see group_table below)."""
+        return group_table(self, named_params, spec, default_wd)
+
+
+# ---- parameter groups ------------------------------------------------------------------------------------------------------
+# A spec is plain data (it travels in checkpoints):
+#   [{"match": regex | [parameter names], "lr_scale": None | float, "weight_decay": None | float, "frozen": None | bool}, ...]
+# matched with re.search against the names of named_parameters() (the reference's names).  Every field resolves on its own: a
+# parameter takes each of lr_scale / weight_decay / frozen from the FIRST entry that matches it AND sets that field (not None);
+# what no entry sets is the default {1.0, the optimizer's weight_decay, False}.  With entries that set all three fields this is
+# "the first matching entry wins"; with entries that set one field each, a parameter can be both scaled and un-decayed.
+# A parameter reachable under several names (the tied embedding / LM head, the attention weights tied by init_attn_weight) is known
+# by its FIRST name in named_parameters() only; an entry that matches no parameter raises (a silent typo is worse).
+_SPEC_FIELDS = ("lr_scale", "weight_decay", "frozen")
+BLOCK = 1024        # elements per first_seg entry (arena sizes are multiples of it)
+
+
+def normalize_spec(spec):
+    """validated plain-data copy of a spec (None stays None)."""
+    if spec is None:
+        return None
+    out = []
+    for k, e in enumerate(spec):
+        if not isinstance(e, dict) or "match" not in e or set(e) - {"match", *_SPEC_FIELDS}:
+            raise ValueError(f"param_groups[{k}]: an entry is a dict with 'match' and any of {_SPEC_FIELDS}, got {e!r}")
+        m = e["match"]
+        if isinstance(m, str):
+            import re
+            try:
+                re.compile(m)
+            except re.error as err:
+                raise ValueError(f"param_groups[{k}]: bad regex {m!r}: {err}") from None
+        else:
+            m = [str(x) for x in m]
+            if not m:
+                raise ValueError(f"param_groups[{k}]: empty name list")
+        lr, wd, fr = e.get("lr_scale"), e.get("weight_decay"), e.get("frozen")
+        if lr is not None and not (float(lr) >= 0.0 and float(lr) < float("inf")):
+            raise ValueError(f"param_groups[{k}]: lr_scale={lr!r} must be a finite number >= 0")
+        if wd is not None and not (float(wd) >= 0.0 and float(wd) < float("inf")):
+            raise ValueError(f"param_groups[{k}]: weight_decay={wd!r} must be a finite number >= 0")
+        if lr is None and wd is None and fr is None:
+            raise ValueError(f"param_groups[{k}]: the entry sets none of {_SPEC_FIELDS}")
+        out.append({"match": m, "lr_scale": None if lr is None else float(lr), "weight_decay": None if wd is None else float(wd),
+                    "frozen": None if fr is None else bool(fr)})
+    # two explicit name lists that set the same field for the same name: the second could never apply — almost surely a mistake
+    for i, a in enumerate(out):
+        for j in range(i + 1, len(out)):
+            b = out[j]
+            if isinstance(a["match"], list) and isinstance(b["match"], list):
+                both = sorted(set(a["match"]) & set(b["match"]))
+                same = [f for f in _SPEC_FIELDS if a[f] is not None and b[f] is not None]
+                if both and same:
+                    raise ValueError(f"param_groups[{i}] and [{j}] both list {both[:3]} and both set {same}")
+    return out
+
+
+def resolve_spec(names, spec, default_wd):
+    """{name: (lr_scale, weight_decay, frozen)} for the given (first) parameter names; raises for an entry that matches none."""
+    import re
+    spec = normalize_spec(spec) or []
+    names = list(names)
+    known = set(names)
+    hits = []
+    for k, e in enumerate(spec):
+        if isinstance(e["match"], list):
+            unknown = [x for x in e["match"] if x not in known]
+            if unknown:
+                raise ValueError(f"param_groups[{k}]: {unknown[:3]} name no parameter of this optimizer (a tied parameter is known by "
+                                 "its first name in named_parameters() only)")
+            hit = set(e["match"])
+        else:
+            rx = re.compile(e["match"])
+            hit = {x for x in names if rx.search(x)}
+            if not hit:
+                raise ValueError(f"param_groups[{k}]: {e['match']!r} matches no parameter of this optimizer")
+        hits.append(hit)
+    out = {}
+    for x in names:
+        val = {"lr_scale": 1.0, "weight_decay": float(default_wd), "frozen": False}
+        for f in _SPEC_FIELDS:
+            for e, hit in zip(spec, hits):
+                if e[f] is not None and x in hit:
+                    val[f] = e[f]
+                    break
+        out[x] = (val["lr_scale"], val["weight_decay"], val["frozen"])
+    return out
+
+
+class GroupTable:
+    """the three tensors the grouped AdamW / clip-norm kernels read (include/vacnic_hip.h), on the host until .to(device)."""
+
+    def __init__(self, seg_start, seg, first_seg):
+        self.seg_start, self.seg, self.first_seg = seg_start, seg, first_seg
+        self.nseg = seg.shape[0]
+
+    def to(self, device):
+        return GroupTable(self.seg_start.to(device), self.seg.to(device), self.first_seg.to(device))
+
+    def segments(self):
+        """[(start, end, lr_scale, weight_decay, frozen)]"""
+        s, v = self.seg_start.tolist(), self.seg.cpu()
+        fr = v.view(torch.int32)[:, 2].tolist()
+        return [(s[i], s[i + 1], float(v[i, 0]), float(v[i, 1]), bool(fr[i])) for i in range(self.nseg)]
+
+
+def table_from_segments(n, segments):
+    """GroupTable over [0, n) from [(start, lr_scale, weight_decay, frozen)]: adjacent segments with equal values are merged, and
+    the starts must ascend strictly from 0 and stay below n (so the segments tile [0, n) without overlap)."""
+    if not segments or segments[0][0] != 0:
+        raise ValueError("group table: the first segment must start at element 0")
+    merged, prev = [], -1
+    for start, lr, wd, fr in segments:
+        if start <= prev:
+            raise ValueError(f"group table: segment starts must ascend strictly ({prev} then {start})")
+        prev = start
+        if not 0 <= start < n:
+            raise ValueError(f"group table: segment start {start} outside [0, {n})")
+        val = (float(lr), float(wd), bool(fr))
+        if merged and merged[-1][1] == val:
+            continue
+        merged.append((int(start), val))
+    seg_start = torch.tensor([s for s, _ in merged] + [int(n)], dtype=torch.int64)
+    seg = torch.zeros(len(merged), 4, dtype=torch.float32)
+    seg[:, 0] = torch.tensor([v[0] for _, v in merged], dtype=torch.float32)
+    seg[:, 1] = torch.tensor([v[1] for _, v in merged], dtype=torch.float32)
+    seg.view(torch.int32)[:, 2] = torch.tensor([int(v[2]) for _, v in merged], dtype=torch.int32)
+    assert bool((seg_start[1:] > seg_start[:-1]).all()) and int(seg_start[0]) == 0 and int(seg_start[-1]) == n
+    blocks = torch.arange(0, (n + BLOCK - 1) // BLOCK, dtype=torch.int64) * BLOCK
+    first_seg = (torch.searchsorted(seg_start, blocks, right=True) - 1).to(torch.int32)       # the segment holding element 1024 b
+    return GroupTable(seg_start, seg, first_seg)
+
+
+def first_names(arena, named_params):
+    """[(first name, parameter)] of the arena's parameters in named_params order; parameters of other arenas are skipped."""
+    out, seen = [], set()
+    for name, p in named_params:
+        if id(p) in arena.slots and id(p) not in seen:
+            seen.add(id(p))
+            out.append((name, p))
+    missing = [i for i in arena.slots if i not in seen]
+    if missing:
+        raise ValueError(f"group table: {len(missing)} parameter(s) of the arena are not in named_params")
+    return out
+
+
+def group_table(arena, named_params, spec, default_wd):
+    """Lay a spec over the arena's slots.  Alignment gaps, the pad_rows padding of a slot and the tail up to arena.n belong to the
+    preceding parameter's segment (they hold p = g = m = v = 0 and stay 0 under any group: 0 * decay - lr * 0 / (0 + eps) = 0).
+    Pure host logic: works on a "cpu" arena; the optimizer uploads the result once."""
+    named = first_names(arena, named_params)
+    vals = resolve_spec([nm for nm, _ in named], spec, default_wd)
+    slots = sorted((arena.slots[id(p)][0], vals[nm]) for nm, p in named)
+    if slots[0][0] != 0:
+        raise ValueError("group table: the arena's first slot does not start at element 0")
+    return table_from_segments(arena.n, [(o, *v) for o, v in slots])
+
+
+def no_decay_spec(model):
+    """[{"match": [names], "weight_decay": 0.0}] for every `.bias` and every parameter of an nn.LayerNorm — chosen by module type
+    and attribute, not by name pattern (BART's LayerNorms are `*_layer_norm` and `layernorm_embedding*`).  The frozen CLIP tower
+    (`clip_model.*`) has its own arena and is left out."""
+    first = {}
+    for name, p in model.named_parameters():
+        first.setdefault(id(p), name)
+    names = []
+    for mod in model.modules():
+        for attr, p in mod._parameters.items():
+            if p is None or not (attr == "bias" or isinstance(mod, torch.nn.LayerNorm)):
+                continue
+            nm = first[id(p)]
+            if not nm.startswith("clip_model.") and nm not in names:
+                names.append(nm)
+    if not names:
+        raise ValueError("no_decay_spec: the model has neither biases nor LayerNorms")
+    return [{"match": names, "weight_decay": 0.0}]

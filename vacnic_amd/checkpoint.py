@@ -9,7 +9,8 @@ agree to ~1e-3 because a step itself is not run-to-run deterministic: the split-
 embedding scatter sum through fp32 atomics whose order varies (VACNIC_WGRAD_GROUP_MAX_M=1000000 removes the first source):
   model      {reference parameter name: fp32 tensor}   (the fp32 master copies; the bf16 shadow is derived)
   optimizer  {"exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}, "lr": float, "step": int}   — torch.optim.AdamW layout
-  schedule   {"base_lr", "num_warmup_steps", "num_training_steps"}
+  schedule   {"base_lr", "num_warmup_steps", "num_training_steps", ...; "param_groups": the optimizer's parameter-group spec as plain
+             data — present only when it has one; loading into an optimizer with another spec (or none) raises}
   rng        {"seed", "counter", "device_counter"}      — Philox dropout seeds (ops.Rng); `seed` is rank-free, rank r uses seed + r
   meta       {"format": 1, "step": int, ...caller extras}
 Everything is moved to the CPU before `torch.save`, so a checkpoint loads on any box."""
@@ -66,6 +67,9 @@ def save_checkpoint(path, model, optimizer=None, step=0, rank=0, **extra):
         ck["optimizer"] = optimizer_state(model, optimizer)
         ck["schedule"] = {"base_lr": optimizer.lr, "num_warmup_steps": optimizer.warmup, "num_training_steps": optimizer.total,
                           "weight_decay": optimizer.wd, "betas": tuple(optimizer.betas), "eps": optimizer.eps}
+        if getattr(optimizer, "param_groups", None) is not None:
+            ck["schedule"]["param_groups"] = [dict(e, match=list(e["match"]) if isinstance(e["match"], list) else e["match"])
+                                              for e in optimizer.param_groups]
     dev = ops.Rng.dev
     # `seed` is the run's seed WITHOUT the saving rank's offset (the trainer seeds rank r with seed + r): a resumed rank
     # re-derives its own base, so the data-parallel replicas keep drawing different dropout masks
@@ -95,6 +99,10 @@ def load_checkpoint(path_or_dict, model, optimizer=None, strict=True, rank=0):
     if getattr(net, "arena", None) is not None:
         net.arena.refresh_shadow()                       # bf16 compute copies follow the restored fp32 masters
     if optimizer is not None and "optimizer" in ck:
+        # the moments of a parameter mean what its group made of them: resume with the spec the run was started with
+        saved, own = ck.get("schedule", {}).get("param_groups"), getattr(optimizer, "param_groups", None)
+        if saved != own:
+            raise ValueError(f"checkpoint was written with param_groups={saved!r}, the optimizer has param_groups={own!r}")
         a, o = optimizer.arena, ck["optimizer"]
         a.exp_avg.zero_(); a.exp_avg_sq.zero_()
         for name, p in _named_trainable(net):

@@ -96,6 +96,113 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __rest
   }
 }
 
+// ---- parameter groups: per-segment lr multiple / weight decay / frozen flag (include/vacnic_hip.h) ---------------------------
+// Lookup: a thread's 4-vector starts at absolute arena element `a`; first_seg[a >> 10] is the segment holding the first element
+// of that 1024-element block, and the thread walks seg_start forward from there — a few entries at most for a table built from
+// parameters (a block of 1024 elements holds few of them), all of it hits in L2 (the table is < 0.1 % of the streamed bytes).
+struct GroupTable {
+  const int64_t* __restrict__ seg_start; const vacnic_adamw_seg* __restrict__ seg; const int32_t* __restrict__ first_seg;
+  long nseg, nblocks, elem_base;
+};
+// segment of absolute element a; clamped, so a malformed table cannot index outside itself
+__device__ __forceinline__ long seg_of(const GroupTable& t, long a) {
+  long b = a >> 10;
+  b = b < 0 ? 0 : (b >= t.nblocks ? t.nblocks - 1 : b);
+  long s = t.first_seg[b];
+  s = s < 0 ? 0 : (s >= t.nseg ? t.nseg - 1 : s);
+  while (s < t.nseg - 1 && t.seg_start[s + 1] <= a) ++s;
+  return s;
+}
+// first element after segment s (the last segment extends to the end of whatever range is being processed)
+__device__ __forceinline__ long seg_end(const GroupTable& t, long s) { return s < t.nseg - 1 ? t.seg_start[s + 1] : INT64_MAX; }
+
+// adamw_kernel's per-element arithmetic with the multiply-adds it compiles to written out (the compiler is free to contract
+// a * b + c * d either way round; a one-segment table must reproduce adamw_kernel bit for bit, which the tests check):
+//   m = fma(b1, m, (1 - b1) g);  v = fma(b2, v, ((1 - b2) g) g);  p = fma(decay, p, -(step_size m / fma(sqrt(v), 1/sqrt(bc2), eps)))
+//   decay = fma(-lr, wd, 1)
+__device__ __forceinline__ float adam_m(float b1, float m, float gr) { return fmaf(b1, m, (1.f - b1) * gr); }
+__device__ __forceinline__ float adam_v(float b2, float v, float gr) { return fmaf(b2, v, (1.f - b2) * gr * gr); }
+__device__ __forceinline__ float adam_p(float p, float decay, float step_size, float me, float ve, float inv_sqrt_bc2, float eps) {
+  return fmaf(decay, p, -(step_size * me / fmaf(sqrtf(ve), inv_sqrt_bc2, eps)));
+}
+
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                           const float* __restrict__ hyper, long n4, float b1, float b2, float eps,
+                                                           float gscale, int zero_grad, const float* __restrict__ clip,
+                                                           GroupTable tab) {
+  const float lr0 = hyper[0], t = hyper[1];
+  if (clip) gscale *= clip[0];
+  const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
+  const float inv_sqrt_bc2 = rsqrtf(bc2);
+  const long stride = (long)gridDim.x * blockDim.x;
+  // launch shape and per-element arithmetic of adamw_kernel<1>: one segment {1, wd, not frozen} reproduces it bit for bit
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = ((f32x4*)p)[i], gv = ((f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+    const long a = tab.elem_base + (i << 2);
+    long s = seg_of(tab, a);
+    vacnic_adamw_seg sg = tab.seg[s];
+    if (a + 4 <= seg_end(tab, s)) {                     // the whole vector lies in one segment (all but a few vectors per boundary)
+      if (!sg.frozen) {
+        const float lr = lr0 * sg.lr_scale;
+        const float step_size = lr / bc1, decay = fmaf(-lr, sg.weight_decay, 1.f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float gr = gv[e] * gscale;
+          const float me = adam_m(b1, mv[e], gr), ve = adam_v(b2, vv[e], gr);
+          pv[e] = adam_p(pv[e], decay, step_size, me, ve, inv_sqrt_bc2, eps); mv[e] = me; vv[e] = ve;
+        }
+        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+        if (pb) ((u32x2*)pb)[i] = (u32x2){pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3])};
+      }
+    } else {                                            // a boundary inside the vector: element by element, scalar stores
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (a + e >= seg_end(tab, s)) { s = seg_of(tab, a + e); sg = tab.seg[s]; }
+        if (sg.frozen) continue;
+        const float lr = lr0 * sg.lr_scale;
+        const float step_size = lr / bc1, decay = fmaf(-lr, sg.weight_decay, 1.f);
+        const float gr = gv[e] * gscale;
+        const float me = adam_m(b1, mv[e], gr), ve = adam_v(b2, vv[e], gr);
+        const float pe = adam_p(pv[e], decay, step_size, me, ve, inv_sqrt_bc2, eps);
+        const long j = (i << 2) + e;
+        p[j] = pe; m[j] = me; v[j] = ve;
+        if (pb) pb[j] = f2bf(pe);
+      }
+    }
+    if (zero_grad) ((f32x4*)g)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};       // frozen elements too: backward still accumulates into them
+  }
+}
+
+// grad_sumsq_kernel over the non-frozen elements: same grid, same per-thread order, same tree
+__global__ __launch_bounds__(256) void grad_sumsq_groups_kernel(const float* __restrict__ g, long n4, float gscale,
+                                                                float* __restrict__ partials, GroupTable tab) {
+  float acc = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 gv = ((const f32x4*)g)[i];
+    const long a = tab.elem_base + (i << 2);
+    long s = seg_of(tab, a);
+    int frozen = tab.seg[s].frozen;
+    if (a + 4 <= seg_end(tab, s)) {
+      if (!frozen) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float x = gv[e] * gscale; acc = fmaf(x, x, acc); }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (a + e >= seg_end(tab, s)) { s = seg_of(tab, a + e); frozen = tab.seg[s].frozen; }
+        if (!frozen) { const float x = gv[e] * gscale; acc = fmaf(x, x, acc); }
+      }
+    }
+  }
+  __shared__ float red[4];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ s, bf16_t* __restrict__ d, long n) {
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -151,6 +258,51 @@ extern "C" int vacnic_grad_clip_coef(const float* g, int64_t n, float grad_scale
   hipLaunchKernelGGL(grad_sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, g, (long)(n >> 2), grad_scale, partials);
   VLAUNCH_CHECK();
   hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, kNormBlocks, max_norm, out);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+// ordering and coverage of the table are the host builder's to check (it lives in device memory: reading it here would sync)
+#define VCHECK_GROUP_TABLE(a, what)                                                                                              \
+  VCHECK((a)->seg_start && (a)->seg && (a)->first_seg, VACNIC_BAD_SHAPE, what ": null group table");                             \
+  VCHECK((a)->nseg >= 1 && (a)->nblocks >= 1 && (a)->elem_base >= 0, VACNIC_BAD_SHAPE,                                           \
+         what ": nseg=%ld and nblocks=%ld must be >= 1, elem_base=%ld >= 0", (long)(a)->nseg, (long)(a)->nblocks,                \
+         (long)(a)->elem_base);                                                                                                  \
+  VCHECK((a)->elem_base + (a)->n <= (a)->nblocks * 1024, VACNIC_BAD_SHAPE,                                                       \
+         what ": elements [%ld, %ld) lie outside the table's %ld blocks of 1024", (long)(a)->elem_base,                          \
+         (long)((a)->elem_base + (a)->n), (long)(a)->nblocks)
+
+extern "C" int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_adamw_groups, a, stream);
+  VCHECK(a && a->p && a->g && a->m && a->v && a->hyper, VACNIC_BAD_SHAPE, "adamw_groups: null operand");
+  VCHECK(a->n >= 0 && (a->n & 3) == 0, VACNIC_BAD_SHAPE, "adamw_groups: n=%ld must be a multiple of 4 (pad the arena)", (long)a->n);
+  VCHECK(aligned16(a->p) && aligned16(a->g) && aligned16(a->m) && aligned16(a->v) && (!a->p_bf16 || (((uintptr_t)a->p_bf16) & 7) == 0),
+         VACNIC_MISALIGNED, "adamw_groups: arenas must be 16-byte aligned");
+  VCHECK_GROUP_TABLE(a, "adamw_groups");
+  if (a->n == 0) return VACNIC_OK;
+  const long n4 = a->n >> 2;
+  unsigned blocks = 65536;                     // the launch shape of vacnic_adamw
+  const long need = (n4 + 255) / 256;
+  if (need < blocks) blocks = (unsigned)(need < 1 ? 1 : need);
+  const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
+                     (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->grad_scale, a->zero_grad, a->clip_coef, tab);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_grad_clip_coef_groups, a, stream);
+  VCHECK(a && a->g && a->partials && a->out, VACNIC_BAD_SHAPE, "grad_clip_coef_groups: null operand");
+  VCHECK(a->n >= 0 && (a->n & 3) == 0 && aligned16(a->g), VACNIC_BAD_SHAPE,
+         "grad_clip_coef_groups: arena must be 16-byte aligned, n=%ld a multiple of 4", (long)a->n);
+  VCHECK(a->max_norm > 0.f, VACNIC_BAD_SHAPE, "grad_clip_coef_groups: max_norm must be > 0");
+  VCHECK_GROUP_TABLE(a, "grad_clip_coef_groups");
+  const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
+  hipLaunchKernelGGL(grad_sumsq_groups_kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, a->g, (long)(a->n >> 2),
+                     a->grad_scale, a->partials, tab);
+  VLAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, kNormBlocks, a->max_norm, a->out);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

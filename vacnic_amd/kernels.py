@@ -557,6 +557,32 @@ def grad_clip_coef(g, n, max_norm, grad_scale=1.0, partials=None, out=None):
     return out
 
 
+def _group_table(table, elem_base):
+    """struct fields of a device-resident parameter-group table (arena.group_table(...).to(device))."""
+    return dict(seg_start=_p(table.seg_start), seg=_p(table.seg), first_seg=_p(table.first_seg), nseg=table.nseg,
+                nblocks=table.first_seg.numel(), elem_base=elem_base)
+
+
+def adamw_groups(p, g, m, v, p16, hyper, n, table, elem_base=0, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, zero_grad=True,
+                 clip_coef=None):
+    """adamw() with per-segment lr multiple / weight decay / frozen flag; p, g, m, v, p16 start at arena element elem_base."""
+    call_struct("vacnic_adamw_groups", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
+                n=n, beta1=beta1, beta2=beta2, eps=eps, grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef),
+                **_group_table(table, elem_base))
+
+
+def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0):
+    """grad_clip_coef() over the non-frozen segments of the table."""
+    if partials is None:
+        partials = torch.empty(1024, device=g.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(2, device=g.device, dtype=torch.float32)
+    assert g.dtype == torch.float32 and partials.numel() >= 1024 and out.numel() >= 2
+    call_struct("vacnic_grad_clip_coef_groups", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=max_norm,
+                partials=_p(partials), out=_p(out), **_group_table(table, elem_base))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- misc
 def cast_f32_bf16(src, dst=None):
     if dst is None:

@@ -31,6 +31,22 @@ class TrainArgs:
     no_clip_norm: bool = True
     clip_norm: float = 0.1
     prompt_mlp_type: str = "clipcap"
+    # parameter groups (param_group_spec): all off = one learning rate and one weight decay for every parameter, nothing frozen
+    no_decay_bias_ln: bool = False        # --no_decay_bias_ln: weight decay 0 on every bias and LayerNorm parameter
+    lr_scale: tuple = ()                  # --lr_scale REGEX=FLOAT (repeatable): ((regex, multiple of the scheduled lr), ...)
+    freeze: tuple = ()                    # --freeze REGEX (repeatable)
+
+
+def param_group_spec(model, args: TrainArgs):
+    """FusedAdamW(param_groups=...) for the trainers' three flags, or None when all are off.  Order: freeze, then lr_scale, then
+    no-decay; every entry sets ONE field and every field resolves by its own first match (arena.resolve_spec), so a parameter can be
+    scaled AND un-decayed, and a frozen one stays frozen whatever else matches it."""
+    from .arena import no_decay_spec
+    spec = [{"match": rx, "frozen": True} for rx in args.freeze]
+    spec += [{"match": rx, "lr_scale": float(f)} for rx, f in args.lr_scale]
+    if args.no_decay_bias_ln:
+        spec += no_decay_spec(model.module if isinstance(model, DistributedDataParallel) else model)
+    return spec or None
 
 
 class FusedAdamW:
@@ -38,7 +54,12 @@ class FusedAdamW:
     gradient arena: one lr kernel + one AdamW kernel per step, lr and step counter in device memory."""
 
     def __init__(self, arena, lr, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, num_warmup_steps=0.0,
-                 num_training_steps=1.0, world_size=1):
+                 num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None):
+        """param_groups: a spec (arena.py "parameter groups") giving ranges of the arena their own multiple of the scheduled learning
+        rate, their own weight decay, or freezing them — torch.optim.AdamW(param_groups) under one LambdaLR; it needs
+        named_parameters=model.named_parameters() to match against.  A frozen parameter keeps p, m, v and its bf16 shadow untouched,
+        its gradient is still computed by backward and zeroed by the step, and it does not count in the clip norm.
+        None (default): one group, the ungrouped kernels."""
         self.arena = arena
         arena.init_optimizer_state()
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
@@ -47,6 +68,14 @@ class FusedAdamW:
         self.hyper = torch.zeros(2, device=arena.device, dtype=torch.float32)      # {lr, step}
         self.clip = None                  # {clip coefficient, total grad norm} of the last clipped step (device)
         self._clip_scratch = None
+        self.param_groups, self.table = None, None
+        if param_groups is not None:
+            from .arena import normalize_spec
+            if named_parameters is None:
+                raise ValueError("FusedAdamW(param_groups=...) needs named_parameters=model.named_parameters()")
+            self.param_groups = normalize_spec(param_groups)                 # plain data: state_dict() and checkpoints carry it
+            # built and validated on the host, uploaded once: no per-step host work
+            self.table = arena.group_table(named_parameters, self.param_groups, weight_decay).to(arena.device)
 
     def step(self, clip_norm=None):
         """clip_norm: max total gradient norm (torch.nn.utils.clip_grad_norm_, TRAIN:365-366) or None.  The norm is taken
@@ -59,9 +88,16 @@ class FusedAdamW:
             if self.clip is None:
                 self.clip = torch.zeros(2, device=a.device, dtype=torch.float32)
                 self._clip_scratch = torch.empty(1024, device=a.device, dtype=torch.float32)
-            clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
-        K.adamw(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.betas[0], self.betas[1],
-                self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip)
+            if self.table is None:
+                clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
+            else:
+                clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
+        if self.table is None:
+            K.adamw(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.betas[0], self.betas[1],
+                    self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip)
+        else:
+            K.adamw_groups(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.table, 0, self.betas[0],
+                           self.betas[1], self.eps, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip)
 
     def begin_step(self):
         """first half of step() for a range-wise update (DistributedDataParallel.reduce_and_step): schedule + counters once."""
@@ -70,14 +106,22 @@ class FusedAdamW:
     def step_range(self, start, end):
         """AdamW on arena elements [start, end) (a DDP bucket whose all-reduce has finished); begin_step() comes first."""
         a = self.arena
-        K.adamw(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end], self.hyper,
-                end - start, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
+        if self.table is None:
+            K.adamw(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end], self.hyper,
+                    end - start, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
+        else:
+            K.adamw_groups(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end],
+                           self.hyper, end - start, self.table, start, self.betas[0], self.betas[1], self.eps,
+                           grad_scale=1.0 / self.world, zero_grad=True)
 
     def zero_grad(self):
         pass            # fused into step(): the AdamW kernel clears the gradient arena it just consumed
 
     def state_dict(self):
-        return {"exp_avg": self.arena.exp_avg, "exp_avg_sq": self.arena.exp_avg_sq, "hyper": self.hyper}
+        sd = {"exp_avg": self.arena.exp_avg, "exp_avg_sq": self.arena.exp_avg_sq, "hyper": self.hyper}
+        if self.param_groups is not None:
+            sd["param_groups"] = self.param_groups
+        return sd
 
 
 def build_models(cfg: VacnicConfig, vcfg: ClipVisionConfig, device="cuda", seed=0, init="device", state_dicts=None, with_guide=True):
