@@ -332,11 +332,14 @@ int vacnic_name_embed_mean(const vacnic_name_embed_args* a, void* stream);
  * Also refreshes the bf16 shadow and zeroes the gradient.  grad_scale multiplies g first
  * (1/world_size for DDP averaging).  clip_coef (may be NULL): device pointer to the clip_grad_norm_
  * coefficient written by vacnic_grad_clip_coef; it multiplies g after grad_scale.
+ * skip (may be NULL = never): device pointer to the verdict of vacnic_grad_guard (its state[0]).  When *skip != 0 the kernel
+ * writes no p, m, v and no shadow (no weight decay either) and only zeroes g when zero_grad.
  */
 typedef struct {
   float* p; float* g; float* m; float* v; void* p_bf16; const float* hyper;
   int64_t n; float beta1, beta2, eps, weight_decay, grad_scale; int32_t zero_grad;
   const float* clip_coef;
+  const int64_t* skip;
 } vacnic_adamw_args;
 int vacnic_adamw(const vacnic_adamw_args* a, void* stream);
 /* torch.nn.utils.clip_grad_norm_(model.parameters(), clip_norm) (TRAIN:365-366) over the flat gradient arena,
@@ -365,6 +368,7 @@ typedef struct {
   const float* clip_coef;
   const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
   int64_t nseg, nblocks, elem_base;
+  const int64_t* skip;                 /* as vacnic_adamw_args.skip */
 } vacnic_adamw_groups_args;
 int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stream);
 /* vacnic_grad_clip_coef over the non-frozen elements only (clip_grad_norm_ sees no gradient for a parameter left out of the
@@ -376,6 +380,32 @@ typedef struct {
   int64_t nseg, nblocks, elem_base;
 } vacnic_grad_clip_groups_args;
 int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* a, void* stream);
+/*
+ * Non-finite gradient guard, decided on the device (no host sync; recordable in a launch plan).  Call it between vacnic_lr_step
+ * and vacnic_adamw[_groups], and pass `state` as their `skip`.  Two passes, as vacnic_grad_clip_coef[_groups] (null table
+ * pointers: ungrouped; otherwise frozen segments are left out):
+ *   pass 1  the same fixed grid, per-thread order and reduction tree: partials[1024] are bitwise those of the clip-norm pass;
+ *           first_idx[1024] (int64) gets, per block, the smallest ABSOLUTE arena element index (elem_base + offset in g) whose
+ *           scaled gradient x = g * grad_scale has a non-finite square (NaN, +-Inf, or |x| > ~1.8e19), INT64_MAX if none
+ *   pass 2  skip <=> the fp32 sum of squares is not finite.  Squares cannot cancel, so that is exactly: some element's square is
+ *           non-finite, or the fp32 sum overflowed although every square is finite (||g|| > ~1.8e19) — then no single element is
+ *           to blame and the index reported is -1.
+ *   out    float[2]  {min(1, max_norm / (norm + 1e-6)), norm} — for a finite gradient bitwise what vacnic_grad_clip_coef[_groups]
+ *                    writes; max_norm <= 0 means no clipping: coefficient 1
+ *   state  int64[4]  [0] skip flag of this step   [1] steps skipped so far   [2] current run of consecutive skips (a finite
+ *                    step resets it)   [3] first non-finite element index of the most recent skipped step (-1: none yet, or
+ *                    only the sum overflowed).  The caller initialises it to {0, 0, 0, -1}.
+ *   hyper            on a skip hyper[1] -= 1, undoing vacnic_lr_step's increment: a dropped step advances neither Adam's t nor
+ *                    the schedule position (the next vacnic_lr_step recomputes hyper[0] from the same k).  The dropout counter
+ *                    that vacnic_lr_step advanced stays advanced: the retried position draws fresh masks.
+ */
+typedef struct {
+  const float* g; int64_t n; float grad_scale, max_norm; float* partials; int64_t* first_idx; float* out; int64_t* state;
+  float* hyper;
+  const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
+  int64_t nseg, nblocks, elem_base;
+} vacnic_grad_guard_args;
+int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream);
 /* get_linear_schedule_with_warmup on device (TRAIN:99-107): hyper[0] <- base_lr*lambda(k), hyper[1] <- k+1
  * where k = hyper[1] on entry = optimizer steps already taken.  Also increments *rng_counter (the device-side
  * dropout counter, may be NULL).  Call once before vacnic_adamw. */

@@ -89,6 +89,11 @@ parser.add_argument("--lr_scale", action="append", default=[], metavar="REGEX=FL
                     "FLOAT times the scheduled learning rate, e.g. 'prompt_mlp|visual_map=10' (repeatable; the first match wins)")
 parser.add_argument("--freeze", action="append", default=[], metavar="REGEX", help="parameters whose name matches REGEX are not "
                     "updated (repeatable); their gradients are still computed")
+# non-finite gradient guard of the optimizer (FusedAdamW(skip_nonfinite=True)); off by default = no check, as in the reference
+parser.add_argument("--skip_nonfinite", default=False, type=_b, help="drop (and count) an optimizer step whose gradient holds a NaN or "
+                    "an Inf, decided on the device: weights, moments and the schedule position stay, the gradient is zeroed")
+parser.add_argument("--max_consecutive_skips", type=int, default=8, help="with --skip_nonfinite: stop the run, before any checkpoint "
+                    "is written, once this many steps in a row were dropped")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -124,7 +129,8 @@ def train_args(args, total_steps):
                      num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
-                     no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze))
+                     no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze),
+                     skip_nonfinite=args.skip_nonfinite)
 
 
 def run(args, batches=None):
@@ -169,8 +175,18 @@ def run(args, batches=None):
     net = DistributedDataParallel(model, device_ids=[local], output_device=local) if world > 1 else model
     opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay, num_warmup_steps=args.warmup_rate * total_steps,
                      num_training_steps=total_steps, world_size=world, param_groups=param_group_spec(model, targs),
-                     named_parameters=model.named_parameters())
+                     named_parameters=model.named_parameters(), skip_nonfinite=targs.skip_nonfinite)
     step, t0, hist = 0, time.time(), []
+
+    def check_guard():
+        """EVERY rank reads the guard's 32 bytes (one sync), so that all ranks stop together; called at the log interval and
+        before anything is written over a checkpoint."""
+        rep = opt.guard_report(model.named_parameters())
+        if rep["in_a_row"] >= args.max_consecutive_skips:
+            raise RuntimeError(f"step {step}: {rep['in_a_row']} optimizer steps in a row dropped for a non-finite gradient "
+                               f"({rep['skipped']} in all); first non-finite element in {rep['first_nonfinite']} "
+                               f"(arena offset {rep['offset']}).  No checkpoint was written.")
+        return rep
     plans = {}
     min_val_loss = 999.0                      # TRAIN:452
     start_step = 0
@@ -221,12 +237,20 @@ def run(args, batches=None):
             else:
                 out4 = train_step(net, g_, opt, batch, targs, ready)
             step += 1
-            if step % args.log_every == 0 and rank == 0:          # ONE device->host sync per log interval (the reference does 4 per step)
+            rep = check_guard() if targs.skip_nonfinite and step % args.log_every == 0 else None
+            # ONE wait for the device per log interval (the reference does 4 per step); the small reads that follow the first
+            # (guard state, losses, grad norm) find the device idle
+            if step % args.log_every == 0 and rank == 0:
                 tot, txt, secla, colam = out4.tolist()
                 rec = {"step": step, "loss": tot, "text loss": txt, "face name loss": secla, "margin loss": colam,
                        "samples_per_s": round((step - start_step) * args.train_batch_size * world / (time.time() - t0), 2)}
+                if rep is not None:
+                    rec["skipped"] = rep["skipped"]
+                    rec["grad_norm"] = float(opt.clip[1].item())
                 hist.append(rec)
                 print(json.dumps(rec), flush=True)
+        if targs.skip_nonfinite and args.val_steps > 0:
+            check_guard()                                          # a run that went bad keeps its last good checkpoint
         if args.val_steps > 0 and rank == 0:
             # TRAIN:455-470: validation pass per epoch; the best model and its teacher-forced outputs are kept
             vb = (synthetic.make_batch(cfg, args.val_batch_size, S=args.article_max_length, T=min(64, args.caption_max_length),
@@ -251,6 +275,8 @@ def run(args, batches=None):
                 json.dump(tdict, f)
         print(json.dumps({"test captions": len(tdict), "first": tdict[0]["gen"][0][:12] if tdict else []}), flush=True)
     torch.cuda.synchronize()
+    if targs.skip_nonfinite:
+        check_guard()
     if rank == 0 and args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
         from vacnic_amd import checkpoint          # MFULL-named state_dict + optimizer/schedule/RNG (TRAIN:472 pickles the module object)

@@ -148,7 +148,7 @@ DecoderStepArgs = _struct("vacnic_decoder_step_args", [
 AdamwArgs = _struct("vacnic_adamw_args", [
     ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("hyper", vp),
     ("n", i64), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("grad_scale", f32),
-    ("zero_grad", i32), ("clip_coef", vp)])
+    ("zero_grad", i32), ("clip_coef", vp), ("skip", vp)])
 
 # one segment of a parameter-group table (arena.group_table builds the tensors; this is their element layout)
 AdamwSeg = _struct("vacnic_adamw_seg", [("lr_scale", f32), ("weight_decay", f32), ("frozen", i32), ("reserved", i32)])
@@ -158,10 +158,14 @@ _GROUP_TABLE = [("seg_start", vp), ("seg", vp), ("first_seg", vp), ("nseg", i64)
 AdamwGroupsArgs = _struct("vacnic_adamw_groups_args", [
     ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("hyper", vp),
     ("n", i64), ("beta1", f32), ("beta2", f32), ("eps", f32), ("grad_scale", f32),
-    ("zero_grad", i32), ("clip_coef", vp)] + _GROUP_TABLE)
+    ("zero_grad", i32), ("clip_coef", vp)] + _GROUP_TABLE + [("skip", vp)])
 
 GradClipGroupsArgs = _struct("vacnic_grad_clip_groups_args", [
     ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("out", vp)] + _GROUP_TABLE)
+
+GradGuardArgs = _struct("vacnic_grad_guard_args", [
+    ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("first_idx", vp), ("out", vp), ("state", vp),
+    ("hyper", vp)] + _GROUP_TABLE)
 
 # symbol -> argtypes.  EVERY function include/vacnic_hip.h declares must appear here
 # (tests/test_abi.py parses the header and checks both directions).
@@ -174,7 +178,8 @@ _STRUCT_FNS = {
     "vacnic_colam_fwd": ColamFwdArgs, "vacnic_colam_bwd": ColamBwdArgs,
     "vacnic_secla_fwd": SeclaFwdArgs, "vacnic_secla_bwd": SeclaBwdArgs,
     "vacnic_name_embed_mean": NameEmbedArgs, "vacnic_adamw": AdamwArgs,
-    "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
+    "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
+    "vacnic_grad_guard": GradGuardArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
     "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs,
 }
 _PLAIN_FNS = {

@@ -270,6 +270,16 @@ def first_names(arena, named_params):
     return out
 
 
+def name_at(arena, named_params, offset):
+    """first name (first_names: a tied or shared parameter is known by the first of its names) of the parameter whose elements hold
+    arena offset `offset`; None for alignment gaps, pad_rows padding and the arena's tail.  Pure host logic."""
+    for name, p in first_names(arena, named_params):
+        o, n, _ = arena.slots[id(p)]
+        if o <= offset < o + n:
+            return name
+    return None
+
+
 def group_table(arena, named_params, spec, default_wd):
     """Lay a spec over the arena's slots.  Alignment gaps, the pad_rows padding of a slot and the tail up to arena.n belong to the
     preceding parameter's segment (they hold p = g = m = v = 0 and stay 0 under any group: 0 * decay - lr * 0 / (0 + eps) = 0).

@@ -8,7 +8,10 @@ the dropout RNG are restored EXACTLY (the first step after a resume reproduces t
 agree to ~1e-3 because a step itself is not run-to-run deterministic: the split-K weight gradients, the LayerNorm parameter gradients and the
 embedding scatter sum through fp32 atomics whose order varies (VACNIC_WGRAD_GROUP_MAX_M=1000000 removes the first source):
   model      {reference parameter name: fp32 tensor}   (the fp32 master copies; the bf16 shadow is derived)
-  optimizer  {"exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}, "lr": float, "step": int}   — torch.optim.AdamW layout
+  optimizer  {"exp_avg": {name: tensor}, "exp_avg_sq": {name: tensor}, "lr": float, "step": int}   — torch.optim.AdamW layout;
+             with FusedAdamW(skip_nonfinite=True) also "skipped": steps dropped so far (absent = 0; the run of consecutive drops
+             restarts at 0).  "step" counts the steps APPLIED: it lags meta["step"], the trainer's data position, by "skipped";
+             the two are restored separately.
   schedule   {"base_lr", "num_warmup_steps", "num_training_steps", ...; "param_groups": the optimizer's parameter-group spec as plain
              data — present only when it has one; loading into an optimizer with another spec (or none) raises}
   rng        {"seed", "counter", "device_counter"}      — Philox dropout seeds (ops.Rng); `seed` is rank-free, rank r uses seed + r
@@ -57,7 +60,10 @@ def optimizer_state(model, optimizer):
         ea[name] = a.exp_avg[o:o + n].view(p.shape).detach().cpu().clone()
         es[name] = a.exp_avg_sq[o:o + n].view(p.shape).detach().cpu().clone()
     hyper = optimizer.hyper.detach().cpu()
-    return {"exp_avg": ea, "exp_avg_sq": es, "lr": float(hyper[0]), "step": int(hyper[1])}
+    sd = {"exp_avg": ea, "exp_avg_sq": es, "lr": float(hyper[0]), "step": int(hyper[1])}
+    if getattr(optimizer, "guard", None) is not None:
+        sd["skipped"] = int(optimizer.guard[1].item())
+    return sd
 
 
 def save_checkpoint(path, model, optimizer=None, step=0, rank=0, **extra):
@@ -111,6 +117,8 @@ def load_checkpoint(path_or_dict, model, optimizer=None, strict=True, rank=0):
                 a.exp_avg[off:off + n].copy_(o["exp_avg"][name].reshape(-1))
                 a.exp_avg_sq[off:off + n].copy_(o["exp_avg_sq"][name].reshape(-1))
         optimizer.hyper.copy_(torch.tensor([o["lr"], float(o["step"])]))
+        if getattr(optimizer, "guard", None) is not None:
+            optimizer.guard.copy_(torch.tensor([0, int(o.get("skipped", 0)), 0, -1], dtype=torch.int64))
         r = ck.get("rng")
         if r is not None:
             seed = r["seed"] if "seed" in r else r["base"]          # "base": checkpoints written before the per-rank fix

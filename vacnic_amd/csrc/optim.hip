@@ -20,12 +20,21 @@ __global__ void lr_step_kernel(float* hyper, float base_lr, float warmup, float 
   }
 }
 
+// A step that vacnic_grad_guard dropped: p, m, v and the shadow stay as they are (no weight decay either); the gradient is still
+// cleared, or its NaNs would be accumulated into the next step.  *skip is the same for every thread of the launch.
+__device__ __forceinline__ void skipped_step(float* __restrict__ g, long n4, int zero_grad) {
+  if (!zero_grad) return;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) ((f32x4*)g)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
 template <int UNR>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ pb,
                                                     const float* __restrict__ hyper, long n4, float b1, float b2,
                                                     float eps, float wd, float gscale, int zero_grad,
-                                                    const float* __restrict__ clip) {
+                                                    const float* __restrict__ clip, const int64_t* __restrict__ skip) {
+  if (skip && *skip) { skipped_step(g, n4, zero_grad); return; }       // grad_guard's verdict: one uniform branch
   const float lr = hyper[0], t = hyper[1];
   if (clip) gscale *= clip[0];                  // clip_grad_norm_'s coefficient, computed on device by grad_clip_coef
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
@@ -130,7 +139,8 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
                                                            float* __restrict__ v, bf16_t* __restrict__ pb,
                                                            const float* __restrict__ hyper, long n4, float b1, float b2, float eps,
                                                            float gscale, int zero_grad, const float* __restrict__ clip,
-                                                           GroupTable tab) {
+                                                           GroupTable tab, const int64_t* __restrict__ skip) {
+  if (skip && *skip) { skipped_step(g, n4, zero_grad); return; }
   const float lr0 = hyper[0], t = hyper[1];
   if (clip) gscale *= clip[0];
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
@@ -203,6 +213,111 @@ __global__ __launch_bounds__(256) void grad_sumsq_groups_kernel(const float* __r
   if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- non-finite gradient guard (vacnic_grad_guard, include/vacnic_hip.h) -----------------------------------------------------
+// Pass 1 = grad_sumsq_kernel / grad_sumsq_groups_kernel (same grid, same per-thread order, same tree: the partial sums are theirs
+// bit for bit) that also keeps, per block, the smallest absolute element index whose scaled gradient has a non-finite square.
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ long wave_min_i64(long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const long w = __shfl_xor((long long)v, o, 64); v = w < v ? w : v; }
+  return v;
+}
+// block reduction of the (sum, smallest index) pair, the clip-norm kernels' tree for the sum; the result is thread 0's
+__device__ __forceinline__ void guard_block_reduce(float& acc, long& first) {
+  __shared__ float red[4];
+  __shared__ long redi[4];
+  acc = wave_sum(acc);
+  first = wave_min_i64(first);
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; redi[threadIdx.x >> 6] = first; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    acc = (red[0] + red[1]) + (red[2] + red[3]);
+    const long a = redi[0] < redi[1] ? redi[0] : redi[1], b = redi[2] < redi[3] ? redi[2] : redi[3];
+    first = a < b ? a : b;
+  }
+}
+__global__ __launch_bounds__(256) void grad_guard_sumsq_kernel(const float* __restrict__ g, long n4, float gscale, long elem_base,
+                                                               float* __restrict__ partials, int64_t* __restrict__ first_idx) {
+  float acc = 0.f;
+  long first = INT64_MAX;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 gv = ((const f32x4*)g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = gv[e] * gscale;
+      acc = fmaf(x, x, acc);
+      const long a = elem_base + (i << 2) + e;              // i rises and e rises: the first hit of a thread is its smallest
+      if (nonfinite(x * x) && a < first) first = a;
+    }
+  }
+  guard_block_reduce(acc, first);
+  if (threadIdx.x == 0) { partials[blockIdx.x] = acc; first_idx[blockIdx.x] = first; }
+}
+__global__ __launch_bounds__(256) void grad_guard_sumsq_groups_kernel(const float* __restrict__ g, long n4, float gscale,
+                                                                      float* __restrict__ partials, int64_t* __restrict__ first_idx,
+                                                                      GroupTable tab) {
+  float acc = 0.f;
+  long first = INT64_MAX;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 gv = ((const f32x4*)g)[i];
+    const long a = tab.elem_base + (i << 2);
+    long s = seg_of(tab, a);
+    int frozen = tab.seg[s].frozen;
+    if (a + 4 <= seg_end(tab, s)) {
+      if (!frozen) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float x = gv[e] * gscale;
+          acc = fmaf(x, x, acc);
+          if (nonfinite(x * x) && a + e < first) first = a + e;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (a + e >= seg_end(tab, s)) { s = seg_of(tab, a + e); frozen = tab.seg[s].frozen; }
+        if (!frozen) {
+          const float x = gv[e] * gscale;
+          acc = fmaf(x, x, acc);
+          if (nonfinite(x * x) && a + e < first) first = a + e;
+        }
+      }
+    }
+  }
+  guard_block_reduce(acc, first);
+  if (threadIdx.x == 0) { partials[blockIdx.x] = acc; first_idx[blockIdx.x] = first; }
+}
+// Pass 2 (one workgroup): grad_clip_coef_kernel's sum and coefficient, the verdict, the counters, and on a skip the undo of
+// lr_step's increment of hyper[1].  skip <=> the sum of squares is not finite: squares cannot cancel, so that holds exactly when
+// some element's square is non-finite or the fp32 sum itself overflowed (then no element is to blame: index -1).
+__global__ __launch_bounds__(256) void grad_guard_verdict_kernel(const float* __restrict__ partials,
+                                                                 const int64_t* __restrict__ first_idx, int nparts, float max_norm,
+                                                                 float* __restrict__ out, int64_t* __restrict__ state,
+                                                                 float* __restrict__ hyper) {
+  float acc = 0.f;
+  long first = INT64_MAX;
+  for (int i = threadIdx.x; i < nparts; i += 256) {
+    acc += partials[i];
+    const long f = first_idx[i];
+    first = f < first ? f : first;
+  }
+  guard_block_reduce(acc, first);
+  if (threadIdx.x == 0) {
+    const float sumsq = acc;
+    const float norm = sqrtf(sumsq);
+    out[0] = max_norm > 0.f ? fminf(1.f, max_norm / (norm + 1e-6f)) : 1.f;
+    out[1] = norm;
+    const long f = first;
+    if (nonfinite(sumsq)) {
+      state[0] = 1; state[1] += 1; state[2] += 1;
+      state[3] = f == INT64_MAX ? -1 : f;
+      hyper[1] -= 1.f;                       // neither Adam's t nor the schedule position advances on a dropped step
+    } else {
+      state[0] = 0; state[2] = 0;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ s, bf16_t* __restrict__ d, long n) {
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -244,7 +359,7 @@ extern "C" int vacnic_adamw(const vacnic_adamw_args* a, void* stream) {
   if (need < blocks) blocks = (unsigned)(need < 1 ? 1 : need);
   hipLaunchKernelGGL(adamw_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
                      (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->weight_decay, a->grad_scale, a->zero_grad,
-                     a->clip_coef);
+                     a->clip_coef, a->skip);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
@@ -286,7 +401,7 @@ extern "C" int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stre
   if (need < blocks) blocks = (unsigned)(need < 1 ? 1 : need);
   const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
   hipLaunchKernelGGL(adamw_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
-                     (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->grad_scale, a->zero_grad, a->clip_coef, tab);
+                     (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->grad_scale, a->zero_grad, a->clip_coef, tab, a->skip);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
@@ -303,6 +418,30 @@ extern "C" int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* 
                      a->grad_scale, a->partials, tab);
   VLAUNCH_CHECK();
   hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, kNormBlocks, a->max_norm, a->out);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_grad_guard, a, stream);
+  VCHECK(a && a->g && a->partials && a->first_idx && a->out && a->state && a->hyper, VACNIC_BAD_SHAPE, "grad_guard: null operand");
+  VCHECK(a->n >= 0 && (a->n & 3) == 0 && aligned16(a->g), VACNIC_BAD_SHAPE,
+         "grad_guard: arena must be 16-byte aligned, n=%ld a multiple of 4", (long)a->n);
+  VCHECK(a->elem_base >= 0, VACNIC_BAD_SHAPE, "grad_guard: elem_base=%ld must be >= 0", (long)a->elem_base);
+  VCHECK(((uintptr_t)a->first_idx & 7) == 0 && ((uintptr_t)a->state & 7) == 0, VACNIC_MISALIGNED, "grad_guard: first_idx and state must be 8-byte aligned");
+  const bool grouped = a->seg_start || a->seg || a->first_seg;
+  if (grouped) {
+    VCHECK_GROUP_TABLE(a, "grad_guard");
+    const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
+    hipLaunchKernelGGL(grad_guard_sumsq_groups_kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, a->g, (long)(a->n >> 2),
+                       a->grad_scale, a->partials, a->first_idx, tab);
+  } else {
+    hipLaunchKernelGGL(grad_guard_sumsq_kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, a->g, (long)(a->n >> 2),
+                       a->grad_scale, (long)a->elem_base, a->partials, a->first_idx);
+  }
+  VLAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_guard_verdict_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, a->first_idx, kNormBlocks,
+                     a->max_norm, a->out, a->state, a->hyper);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

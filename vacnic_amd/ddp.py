@@ -357,8 +357,9 @@ class DistributedDataParallel(torch.nn.Module):
         launched, each slice as soon as ITS collective has finished.  The buckets backward completes last (prompt MLP, the
         embedding tables: ~1 GB of fp32 gradients that cannot overlap with backward) are still on the links while the
         optimizer's ~5.5 ms of HBM traffic for the other ~2.5 GB runs, instead of after them.  With gradient clipping the global
-        norm needs every bucket first: plain reduce, then one step."""
-        if not self.active or clip_norm is not None:
+        norm needs every bucket first: plain reduce, then one step; so does the non-finite guard (FusedAdamW(skip_nonfinite=True)),
+        whose verdict rests on the whole all-reduced gradient — the same on every rank, which therefore take the same decision."""
+        if not self.active or clip_norm is not None or getattr(optimizer, "skip_nonfinite", False):
             self.reduce_gradients()
             optimizer.step(clip_norm=clip_norm)
             return

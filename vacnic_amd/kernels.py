@@ -540,10 +540,11 @@ def lr_step(hyper, base_lr, warmup, total, rng_counter=None):
 
 
 def adamw(p, g, m, v, p16, hyper, n, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, zero_grad=True,
-          clip_coef=None):
+          clip_coef=None, skip=None):
+    """skip: the int64 state of grad_guard() (or None): when its flag is set the step only zeroes g."""
     call_struct("vacnic_adamw", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
                 n=n, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
-                zero_grad=int(zero_grad), clip_coef=_p(clip_coef))
+                zero_grad=int(zero_grad), clip_coef=_p(clip_coef), skip=_p(skip))
 
 
 def grad_clip_coef(g, n, max_norm, grad_scale=1.0, partials=None, out=None):
@@ -564,11 +565,11 @@ def _group_table(table, elem_base):
 
 
 def adamw_groups(p, g, m, v, p16, hyper, n, table, elem_base=0, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, zero_grad=True,
-                 clip_coef=None):
+                 clip_coef=None, skip=None):
     """adamw() with per-segment lr multiple / weight decay / frozen flag; p, g, m, v, p16 start at arena element elem_base."""
     call_struct("vacnic_adamw_groups", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
                 n=n, beta1=beta1, beta2=beta2, eps=eps, grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef),
-                **_group_table(table, elem_base))
+                skip=_p(skip), **_group_table(table, elem_base))
 
 
 def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0):
@@ -581,6 +582,35 @@ def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, 
     call_struct("vacnic_grad_clip_coef_groups", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=max_norm,
                 partials=_p(partials), out=_p(out), **_group_table(table, elem_base))
     return out
+
+
+def guard_state(device):
+    """the int64[4] state of grad_guard(): {skip flag, skipped total, consecutive skips, first non-finite index (-1: none)}."""
+    return torch.tensor([0, 0, 0, -1], device=device, dtype=torch.int64)
+
+
+def grad_guard(g, n, hyper, state=None, max_norm=0.0, table=None, grad_scale=1.0, partials=None, first_idx=None, out=None,
+               elem_base=0):
+    """Non-finite gradient guard on device (no sync): call between lr_step() and adamw(skip=state).  Writes out = {clip coefficient,
+    norm} as grad_clip_coef[_groups] does (max_norm <= 0: coefficient 1), the verdict and counters into `state`, and on a skip takes
+    lr_step's increment of hyper[1] back.  table: a parameter-group table (frozen segments are left out) or None.
+    Returns (out, state)."""
+    dev = g.device
+    if state is None:
+        state = guard_state(dev)
+    if partials is None:
+        partials = torch.empty(1024, device=dev, dtype=torch.float32)
+    if first_idx is None:
+        first_idx = torch.empty(1024, device=dev, dtype=torch.int64)
+    if out is None:
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+    assert g.dtype == torch.float32 and partials.numel() >= 1024 and out.numel() >= 2
+    assert first_idx.dtype == torch.int64 and first_idx.numel() >= 1024 and state.dtype == torch.int64 and state.numel() >= 4
+    tab = _group_table(table, elem_base) if table is not None else dict(seg_start=None, seg=None, first_seg=None, nseg=0, nblocks=0,
+                                                                        elem_base=elem_base)
+    call_struct("vacnic_grad_guard", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=float(max_norm),
+                partials=_p(partials), first_idx=_p(first_idx), out=_p(out), state=_p(state), hyper=_p(hyper), **tab)
+    return out, state
 
 
 # ------------------------------------------------------------------------------------------------- misc

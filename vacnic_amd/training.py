@@ -35,6 +35,7 @@ class TrainArgs:
     no_decay_bias_ln: bool = False        # --no_decay_bias_ln: weight decay 0 on every bias and LayerNorm parameter
     lr_scale: tuple = ()                  # --lr_scale REGEX=FLOAT (repeatable): ((regex, multiple of the scheduled lr), ...)
     freeze: tuple = ()                    # --freeze REGEX (repeatable)
+    skip_nonfinite: bool = False          # --skip_nonfinite: drop a step whose reduced gradient is not finite (FusedAdamW)
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -54,8 +55,12 @@ class FusedAdamW:
     gradient arena: one lr kernel + one AdamW kernel per step, lr and step counter in device memory."""
 
     def __init__(self, arena, lr, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, num_warmup_steps=0.0,
-                 num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None):
-        """param_groups: a spec (arena.py "parameter groups") giving ranges of the arena their own multiple of the scheduled learning
+                 num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None, skip_nonfinite=False):
+        """skip_nonfinite: a step whose gradient (averaged over the ranks, frozen parameters left out) holds a NaN or an Inf, or
+        whose sum of squares overflows fp32, is dropped whole, decided on the device without a sync (K.grad_guard): p, m, v and
+        the shadow stay, the gradient is zeroed, neither Adam's t nor the schedule position advances, and the step is counted
+        (guard_report()).  Off (default): the launches and results of before.
+        param_groups: a spec (arena.py "parameter groups") giving ranges of the arena their own multiple of the scheduled learning
         rate, their own weight decay, or freezing them — torch.optim.AdamW(param_groups) under one LambdaLR; it needs
         named_parameters=model.named_parameters() to match against.  A frozen parameter keeps p, m, v and its bf16 shadow untouched,
         its gradient is still computed by backward and zeroed by the step, and it does not count in the clip norm.
@@ -76,6 +81,14 @@ class FusedAdamW:
             self.param_groups = normalize_spec(param_groups)                 # plain data: state_dict() and checkpoints carry it
             # built and validated on the host, uploaded once: no per-step host work
             self.table = arena.group_table(named_parameters, self.param_groups, weight_decay).to(arena.device)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guard = None                 # int64 {skip flag, skipped total, consecutive skips, first non-finite arena index}
+        if self.skip_nonfinite:
+            # allocated here, not in the first step: a launch plan replays the recorded addresses
+            self.guard = K.guard_state(arena.device)
+            self.clip = torch.zeros(2, device=arena.device, dtype=torch.float32)
+            self._clip_scratch = torch.empty(1024, device=arena.device, dtype=torch.float32)
+            self._guard_scratch = torch.empty(1024, device=arena.device, dtype=torch.int64)
 
     def step(self, clip_norm=None):
         """clip_norm: max total gradient norm (torch.nn.utils.clip_grad_norm_, TRAIN:365-366) or None.  The norm is taken
@@ -84,7 +97,12 @@ class FusedAdamW:
         a = self.arena
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())   # also advances the dropout counter
         clip = None
-        if clip_norm is not None:
+        if self.skip_nonfinite:
+            # the guard's norm pass is the clip's: one pass gives the verdict and {coefficient, norm}
+            K.grad_guard(a.grad, a.n, self.hyper, self.guard, 0.0 if clip_norm is None else float(clip_norm), self.table,
+                         1.0 / self.world, self._clip_scratch, self._guard_scratch, self.clip)
+            clip = None if clip_norm is None else self.clip
+        elif clip_norm is not None:
             if self.clip is None:
                 self.clip = torch.zeros(2, device=a.device, dtype=torch.float32)
                 self._clip_scratch = torch.empty(1024, device=a.device, dtype=torch.float32)
@@ -94,13 +112,29 @@ class FusedAdamW:
                 clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
         if self.table is None:
             K.adamw(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.betas[0], self.betas[1],
-                    self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip)
+                    self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip, skip=self.guard)
         else:
             K.adamw_groups(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.table, 0, self.betas[0],
-                           self.betas[1], self.eps, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip)
+                           self.betas[1], self.eps, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip, skip=self.guard)
+
+    def guard_report(self, named_parameters=None):
+        """The one method of the guard that synchronises (a 32-byte read): {"skipped": steps dropped so far, "in_a_row": current
+        run of consecutive drops, "first_nonfinite": first name (arena.first_names) of the parameter holding the first non-finite
+        gradient element of the most recent dropped step — None if there was none, if only the sum of squares overflowed, if the
+        element lies in padding, or if no named_parameters are given —, "offset": that element's arena index or -1}."""
+        if self.guard is None:
+            raise RuntimeError("guard_report(): the optimizer was built with skip_nonfinite=False")
+        _, skipped, run, first = (int(x) for x in self.guard.tolist())
+        name = None
+        if first >= 0 and named_parameters is not None:
+            from .arena import name_at
+            name = name_at(self.arena, named_parameters, first)
+        return {"skipped": skipped, "in_a_row": run, "first_nonfinite": name, "offset": first}
 
     def begin_step(self):
         """first half of step() for a range-wise update (DistributedDataParallel.reduce_and_step): schedule + counters once."""
+        if self.skip_nonfinite:
+            raise RuntimeError("skip_nonfinite needs the whole reduced gradient before any range is updated: use step()")
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())
 
     def step_range(self, start, end):
@@ -311,7 +345,11 @@ def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towe
     clip = None if args.no_clip_norm else args.clip_norm                         # TRAIN:365-366
     # native reducer: the bucket all-reduces sit ON the weight-gradient stream, and every bucket's AdamW range waits for that
     # bucket's own event — joining the whole stream here would hold AdamW back until the LAST collective has finished
-    pipelined = isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None
+    # (the non-finite guard, like clipping, needs the whole reduced gradient before any range is updated)
+    guarded = getattr(optimizer, "skip_nonfinite", False)
+    if args.skip_nonfinite and not guarded:
+        raise ValueError("TrainArgs.skip_nonfinite needs an optimizer built with FusedAdamW(..., skip_nonfinite=True)")
+    pipelined = isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None and not guarded
     streams.join_all(skip_wgrad=pipelined)   # side streams -> compute stream
     if isinstance(model, DistributedDataParallel):
         model.reduce_and_step(optimizer, clip)       # all-reduce tail overlapped with the optimizer of the finished buckets
