@@ -323,7 +323,7 @@ def attn_probs(q, k, B, H, Tq, Tk, key_mask=None, causal=False, scale=0.125):
 # -------------------------------------------------------------------------------------------- LN family
 def add_ln_fwd(x, residual, gamma, beta, eps=1e-5, p_drop=0.0, seed=0, need_stats=True, seed_dev=None):
     D = x.shape[-1]
-    R = x.numel() // D
+    R = x.numel() // D if D else 0          # D = 0: no rows; the entry point refuses the empty operands
     out = torch.empty_like(x)
     mean = torch.empty(R, device=x.device, dtype=torch.float32) if need_stats else None
     rstd = torch.empty(R, device=x.device, dtype=torch.float32) if need_stats else None
@@ -336,7 +336,7 @@ def add_ln_bwd(dout, x, residual, gamma, mean, rstd, dgamma, dbeta, p_drop=0.0, 
     """fold_on: raw stream for the dgamma / dbeta fold of the two-stage reduction (None: in the call, on the launch stream).  The
     fold is a 5 us kernel nobody in the backward chain waits for; the caller orders `fold_on` behind this launch's stream."""
     D = x.shape[-1]
-    R = x.numel() // D
+    R = x.numel() // D if D else 0          # D = 0: no rows; the entry point refuses the empty operands
     dx = torch.empty_like(x)
     if residual is None or not need_dres:
         dres = None
