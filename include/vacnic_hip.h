@@ -462,6 +462,10 @@ int vacnic_beam_topk(const void* logits, const float* beam_scores, const int32_t
  *   forced_token / top_val / top_idx as in vacnic_beam_topk with K = K2 (n_ban = row length of bans).
  *   workspace: vacnic_lmhead_topk_workspace(R, V, K2) floats of caller-owned scratch (per-workgroup partial results).
  *   forced_token >= 0: no logits are computed (h / emb / workspace may be NULL): the forced token scores beam_scores[r], the rest -inf.
+ *   vacnic_lmhead_topk_supported(R, V, d, K2): 1 if the call accepts this shape, else 0 (VACNIC_UNSUPPORTED): 1 <= R <= 8, d a multiple
+ *   of 8 up to 1024, V <= 65536, K2 <= min(64, V), and the merge's G x K2 candidates (8 bytes each, G = workgroups of the part kernel,
+ *   449 at V = 50265) fit the 160 KiB of LDS: K2 <= 45 at V = 50265.  Callers choose between this call and the GEMM -> vacnic_beam_topk
+ *   chain with it.
  */
 typedef struct {
   const void* h; const void* emb; const float* bias; float* logits; float* workspace;
@@ -470,6 +474,7 @@ typedef struct {
   int32_t n_ban, eos, suppress_eos, forced_token, K2;
 } vacnic_lmhead_topk_args;
 int64_t vacnic_lmhead_topk_workspace(int64_t R, int64_t V, int32_t K2);
+int32_t vacnic_lmhead_topk_supported(int64_t R, int64_t V, int64_t d, int32_t K2);
 int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream);
 /*
  * On-device beam-search bookkeeping: what transformers 4.18 BeamSearchScorer.process does on the host between

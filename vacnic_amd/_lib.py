@@ -221,7 +221,7 @@ _PLAIN_FNS = {
 EXPORTED = sorted(list(_STRUCT_FNS) + list(_PLAIN_FNS) + ["vacnic_last_error_string", "vacnic_version", "vacnic_decoder_step_sync_bytes", "vacnic_decoder_step_slots_bytes",
                                                             "vacnic_plan_begin", "vacnic_plan_size", "vacnic_plan_mark",
                                                             "vacnic_gemm_workspace_bytes", "vacnic_gemm_counters", "vacnic_comm_init",
-                                                            "vacnic_lmhead_topk_workspace"])
+                                                            "vacnic_lmhead_topk_workspace", "vacnic_lmhead_topk_supported"])
 
 for _name, _st in _STRUCT_FNS.items():
     _fn = getattr(lib, _name)          # AttributeError here = stale .so: fail loudly
@@ -247,6 +247,8 @@ lib.vacnic_plan_mark.restype = C.c_int64
 lib.vacnic_plan_mark.argtypes = []
 lib.vacnic_lmhead_topk_workspace.restype = C.c_int64
 lib.vacnic_lmhead_topk_workspace.argtypes = [C.c_int64, C.c_int64, C.c_int32]
+lib.vacnic_lmhead_topk_supported.restype = C.c_int32
+lib.vacnic_lmhead_topk_supported.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
 lib.vacnic_gemm_workspace_bytes.restype = C.c_int64
 lib.vacnic_gemm_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
 lib.vacnic_gemm_counters.restype = C.c_int64

@@ -576,7 +576,8 @@ struct BeamP {
   float* beam_scores; int32_t* done; int32_t* hyp_cnt; double* hyp_worst; double* hyp_score; int32_t* hyp_len; int32_t* hyp_seq;
   int64_t* next_ids; int64_t* src_idx; int32_t* bans;
   int nb, K2, Lmax, cur_len, V, eos, pad, ngram, early;
-  float length_penalty;
+  double lenpow;      // cur_len ^ length_penalty from the HOST's pow: the device's is an ulp off for some lengths (19 ^ 2.0), which moved
+                      // hyp_score off the value transformers computes
 };
 
 // One workgroup per batch item, one wave per beam: wave 0 merges the candidates and does BeamSearchScorer.process, then wave j
@@ -639,7 +640,7 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(BeamP p) {
     if (!is_done) {
       const int nsel = nsel_s;
       // ---- BeamSearchScorer.process: EOS candidates within the first nb ranks finish a hypothesis, the rest continue
-      const double lenpow = pow((double)cur, (double)p.length_penalty);
+      const double lenpow = p.lenpow;
       int cnt = p.hyp_cnt[b]; double worst = p.hyp_worst[b];
       int nch = 0;
       for (int r = 0; r < nsel && nch < nb; ++r) {
@@ -795,6 +796,23 @@ extern "C" int64_t vacnic_lmhead_topk_workspace(int64_t R, int64_t V, int32_t K2
   return G * R * (2 + 2 * (int64_t)K2);
 }
 
+// The merge kernel keeps every workgroup's K2 candidates (value + id) in dynamic LDS next to 48 bytes of static arrays; a CDNA4
+// workgroup may own the CU's whole 160 KiB, above 64 KiB only after the kernel's limit has been raised.
+constexpr size_t LT_LDS_MAX = 160 * 1024, LT_MERGE_STATIC = 64;
+
+static size_t lt_merge_lds(int64_t V, int32_t K2) {
+  const int tpw = lt_tiles_per_wg(V);
+  const int64_t G = ((V + 15) / 16 + tpw - 1) / tpw;
+  return (size_t)G * (size_t)K2 * 8;
+}
+
+extern "C" int32_t vacnic_lmhead_topk_supported(int64_t R, int64_t V, int64_t d, int32_t K2) {
+  if (R < 1 || R > 8 || V <= 0 || K2 < 1 || K2 > 64 || K2 > V) return 0;
+  if (d < 8 || d > 1024 || (d & 7) != 0) return 0;
+  if (lt_tiles_per_wg(V) * 16 > LT_MAXCOLS) return 0;
+  return lt_merge_lds(V, K2) + LT_MERGE_STATIC <= LT_LDS_MAX ? 1 : 0;
+}
+
 extern "C" int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream) {
   VPLAN_REC_STRUCT(vacnic_lmhead_topk, a, stream);
   VCHECK(a && a->top_val && a->top_idx, VACNIC_BAD_SHAPE, "lmhead_topk: null operand");
@@ -821,10 +839,20 @@ extern "C" int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream
   VCHECK(!a->logits || a->ldl >= a->V, VACNIC_BAD_SHAPE, "lmhead_topk: ldl < V");
   VCHECK(a->workspace_floats >= vacnic_lmhead_topk_workspace(a->R, a->V, a->K2), VACNIC_BAD_SHAPE, "lmhead_topk: workspace of %ld floats, need %ld",
          (long)a->workspace_floats, (long)vacnic_lmhead_topk_workspace(a->R, a->V, a->K2));
+  const size_t lds_merge = lt_merge_lds(a->V, a->K2);
+  VCHECK(lds_merge + LT_MERGE_STATIC <= LT_LDS_MAX, VACNIC_UNSUPPORTED, "lmhead_topk: %d workgroups x K2=%d candidates need %ld bytes of LDS in the merge, above %ld",
+         p.G, (int)a->K2, (long)(lds_merge + LT_MERGE_STATIC), (long)LT_LDS_MAX);
+  static bool lds_raised = false;
+  if (lds_merge > 65536 - LT_MERGE_STATIC && !lds_raised) {
+    if (hipFuncSetAttribute((const void*)lmhead_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LT_LDS_MAX - LT_MERGE_STATIC)) != hipSuccess) {
+      vacnic_set_error("lmhead_topk: cannot raise the merge kernel's dynamic LDS limit");
+      return VACNIC_HIP_ERROR;
+    }
+    lds_raised = true;
+  }
   if (a->d > 256) hipLaunchKernelGGL(lmhead_part_kernel<8>, dim3((unsigned)p.G), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(lmhead_part_kernel<2>, dim3((unsigned)p.G), dim3(256), 0, s, p);
   VLAUNCH_CHECK();
-  const size_t lds_merge = (size_t)p.G * a->K2 * 8;
   hipLaunchKernelGGL(lmhead_merge_kernel, dim3((unsigned)a->R), dim3(256), lds_merge, s, p);
   VLAUNCH_CHECK();
   return VACNIC_OK;
@@ -875,7 +903,7 @@ extern "C" int vacnic_beam_step(const vacnic_beam_state* st, const float* top_va
   p.beam_scores = st->beam_scores; p.done = st->done; p.hyp_cnt = st->hyp_cnt; p.hyp_worst = st->hyp_worst; p.hyp_score = st->hyp_score;
   p.hyp_len = st->hyp_len; p.hyp_seq = st->hyp_seq; p.next_ids = st->next_ids; p.src_idx = st->src_idx; p.bans = st->bans;
   p.nb = (int)st->nb; p.K2 = K2; p.Lmax = (int)st->Lmax; p.cur_len = cur_len; p.V = (int)st->V; p.eos = (int)st->eos; p.pad = (int)st->pad;
-  p.ngram = (int)st->no_repeat_ngram_size; p.early = (int)st->early_stopping; p.length_penalty = st->length_penalty;
+  p.ngram = (int)st->no_repeat_ngram_size; p.early = (int)st->early_stopping; p.lenpow = pow((double)cur_len, (double)st->length_penalty);
   hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)st->B), dim3((unsigned)(64 * st->nb)), 0, (hipStream_t)stream, p);
   VLAUNCH_CHECK();
   return VACNIC_OK;

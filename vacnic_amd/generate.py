@@ -344,8 +344,8 @@ class DecodeSession:
         self.h_bans = torch.full((R, max_length), -1, dtype=torch.int32).pin_memory() if ngram > 0 else None
         self.graphs, self.outs, self.pool = {}, {}, None
         # few rows (one caption's beams): the fused LM head + top-k; other shapes: skinny GEMM -> vacnic_beam_topk
-        self.fused_tail = (R <= 8 and model.emb16_pad.shape[1] <= 1024 and model.emb16_pad.shape[1] % 8 == 0 and min(2 * nb, model.V) <= 64
-                           and model.V <= 512 * 128)
+        # (the library's own predicate: at V = 50265 the merge's LDS admits 2 nb <= 45, wider beams take the chain)
+        self.fused_tail = bool(_lib.lib.vacnic_lmhead_topk_supported(R, model.V, model.emb16_pad.shape[1], min(2 * nb, model.V)))
         self.captions = 0
         self.beam = None                  # device-side beam bookkeeping (enable_device_beams)
 

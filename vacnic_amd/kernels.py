@@ -768,3 +768,32 @@ def image_u8_normalize(img_u8, flip=None, mean=(0.48145466, 0.4578275, 0.4082107
 
 def gather_rows(src, dst, idx, rows, row_bytes, row_stride_bytes=0, period=0):
     call("vacnic_gather_rows", _p(src), _p(dst), _p(idx), rows, row_bytes, row_stride_bytes, period, _stream())
+
+
+def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=False, length_penalty=1.0, device="cuda"):
+    """the device state of vacnic_beam_init / vacnic_beam_step (include/vacnic_hip.h) as a namespace of tensors + the C struct `st`."""
+    import types
+    R = B * nb
+    i32 = dict(device=device, dtype=torch.int32)
+    s = types.SimpleNamespace(
+        B=B, nb=nb, Lmax=Lmax, seq=torch.zeros((2, R, Lmax), **i32), beam_scores=torch.zeros(R, device=device, dtype=torch.float32),
+        done=torch.zeros(B, **i32), hyp_cnt=torch.zeros(B, **i32), hyp_worst=torch.zeros(B, device=device, dtype=torch.float64),
+        hyp_score=torch.zeros((B, nb), device=device, dtype=torch.float64), hyp_len=torch.zeros((B, nb), **i32),
+        hyp_seq=torch.zeros((B, nb, Lmax), **i32), next_ids=torch.zeros(R, device=device, dtype=torch.int64),
+        src_idx=torch.zeros(R, device=device, dtype=torch.int64),
+        bans=torch.full((R, Lmax), -1, **i32) if no_repeat_ngram_size > 0 else None)
+    s.st = _lib.BeamState(seq0=s.seq[0].data_ptr(), seq1=s.seq[1].data_ptr(), beam_scores=_p(s.beam_scores), done=_p(s.done),
+                          hyp_cnt=_p(s.hyp_cnt), hyp_worst=_p(s.hyp_worst), hyp_score=_p(s.hyp_score), hyp_len=_p(s.hyp_len),
+                          hyp_seq=_p(s.hyp_seq), next_ids=_p(s.next_ids), src_idx=_p(s.src_idx), bans=_p(s.bans), B=B, nb=nb, Lmax=Lmax,
+                          V=V, eos=eos, pad=pad, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=int(bool(early_stopping)),
+                          length_penalty=float(length_penalty))
+    return s
+
+
+def beam_init(state, start_token):
+    call("vacnic_beam_init", _lib.C.byref(state.st), int(start_token), _stream())
+
+
+def beam_step(state, top_val, top_idx, cur_len):
+    """one position of the on-device beam bookkeeping: top_val f32 / top_idx int32 [B * nb, K2] from beam_topk / lmhead_topk."""
+    call("vacnic_beam_step", _lib.C.byref(state.st), _p(top_val), _p(top_idx), top_val.shape[1], int(cur_len), _stream())
