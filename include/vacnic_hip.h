@@ -371,6 +371,30 @@ typedef struct {
   const int64_t* skip;                 /* as vacnic_adamw_args.skip */
 } vacnic_adamw_groups_args;
 int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stream);
+/*
+ * AdamW with an exponential moving average (EMA) of the weights kept in the same pass.  Null table pointers: the vacnic_adamw
+ * update with `weight_decay`; a table: the vacnic_adamw_groups update (weight_decay is then unused).  p, m, v, the shadow and the
+ * zeroed g are bitwise what those two entry points write for the same inputs.  Every element that is updated also gets
+ *   d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay        t = hyper[1], Adam's step count
+ *   ema = fma(d, ema, (1 - d) * p_new)
+ * (the torch_ema / timm warm-up; a step dropped by vacnic_grad_guard does not advance t).  Elements that are not updated — frozen
+ * segments, and every element when *skip != 0 — leave ema unwritten.  ema is laid out parallel to p: it may point into the
+ * arena's EMA buffer (a DDP bucket) like p, g, m, v, with elem_base the arena offset of p[0].  ema_decay lies in (0, 1).
+ */
+typedef struct {
+  float* p; float* g; float* m; float* v; void* p_bf16; const float* hyper;
+  int64_t n; float beta1, beta2, eps, grad_scale; int32_t zero_grad;
+  const float* clip_coef;
+  const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
+  int64_t nseg, nblocks, elem_base;
+  const int64_t* skip;
+  float weight_decay;
+  float* ema; float ema_decay; int32_t ema_warmup;
+} vacnic_adamw_ema_args;
+int vacnic_adamw_ema(const vacnic_adamw_ema_args* a, void* stream);
+/* Exchange the CONTENTS of p and ema (n fp32 each, n a multiple of 4; addresses stay, so plans, graphs and parameter views hold)
+ * and write p_bf16 = bf16(new p), rounded as vacnic_cast_f32_bf16 rounds (p_bf16 may be NULL).  Two calls restore all three. */
+int vacnic_ema_swap(float* p, float* ema, void* p_bf16, int64_t n, void* stream);
 /* vacnic_grad_clip_coef over the non-frozen elements only (clip_grad_norm_ sees no gradient for a parameter left out of the
  * optimizer): same fixed grid, per-thread order and reduction tree, so with no frozen segment the result is bitwise that of
  * vacnic_grad_clip_coef. */

@@ -69,3 +69,36 @@ for base, names in (("ungrouped K.adamw", [v[0] for v in variants[1:3]]), ("grad
     for name in names:
         r = rows[name]
         print(f"  {name}: mean {sum(r) / len(r):.3f} ms = {sum(r) / len(r) - mean:+.3f} ms against it (rows {', '.join(f'{x:.3f}' for x in r)})")
+
+# ---- moving average of the weights (vacnic_adamw_ema): the same arena with the average kept in the AdamW pass, grouped and
+# ungrouped, beside the plain kernels and beside "plain kernel + a separate pass over p and the average" (torch's lerp_: one
+# elementwise kernel, 8 B read + 4 B written per parameter), rows alternating as above.
+# Traffic model, bytes per parameter: plain 16 read (p, g, m, v) + 18 written (p, m, v, zeroed g, bf16 shadow) = 34;
+# fused average +4 read +4 written = 42; separate pass 34 + 12 = 46 and one more launch.
+ema = p.clone()
+D = 0.999
+ema_variants = [("ungrouped K.adamw", 34, lambda: K.adamw(p, g, m, v, p16, hyper, n, zero_grad=True)),
+                ("ungrouped K.adamw_ema", 42, lambda: K.adamw_ema(p, g, m, v, p16, hyper, n, ema, D, zero_grad=True)),
+                ("ungrouped K.adamw + separate lerp_ pass", 46, lambda: (K.adamw(p, g, m, v, p16, hyper, n, zero_grad=True), ema.lerp_(p, 1.0 - D))),
+                (f"grouped, {real.nseg} segments", 34, lambda: K.adamw_groups(p, g, m, v, p16, hyper, n, real, zero_grad=True)),
+                (f"grouped K.adamw_ema, {real.nseg} segments", 42, lambda: K.adamw_ema(p, g, m, v, p16, hyper, n, ema, D, table=real, zero_grad=True)),
+                ("ema_swap", 18, lambda: K.ema_swap(p, ema, p16))]
+rows = {name: [] for name, _, _ in ema_variants}
+for rep in range(3):
+    for name, _, fn in ema_variants:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        rows[name].append(e0.elapsed_time(e1) / 10)
+        print(f"ema row {rep}: {name}: {rows[name][-1]:.3f} ms (10 launches)")
+base = sum(rows["ungrouped K.adamw"]) / 3
+for name, bpp, _ in ema_variants:
+    r = rows[name]
+    mean = sum(r) / len(r)
+    print(f"{name}: mean {mean:.3f} ms, spread {max(r) - min(r):.3f} ms, {n * bpp / mean / 1e9:.2f} TB/s at {bpp} B/param, "
+          f"{mean / base:.3f} x the ungrouped plain kernel (traffic model: {bpp / 34:.3f})")

@@ -11,6 +11,7 @@ plugs a DataLoader that yields the same batch dict (DSG:22-127) into `run()`.
 One process per GPU: rank/world come from torchrun's env (TRAIN:616-620 uses LOCAL_RANK the same way).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -94,6 +95,11 @@ parser.add_argument("--skip_nonfinite", default=False, type=_b, help="drop (and 
                     "an Inf, decided on the device: weights, moments and the schedule position stay, the gradient is zeroed")
 parser.add_argument("--max_consecutive_skips", type=int, default=8, help="with --skip_nonfinite: stop the run, before any checkpoint "
                     "is written, once this many steps in a row were dropped")
+# moving average of the weights, kept by the AdamW kernel (FusedAdamW(ema_decay=...)); off by default
+parser.add_argument("--ema_decay", type=float, default=0.0, help="exponential moving average of the weights with this decay (e.g. "
+                    "0.999), updated inside the fused AdamW step and stored in the checkpoints; 0 = off")
+parser.add_argument("--ema_eval", default=None, type=_b, help="validation and test captioning run with the averaged weights "
+                    "(default: True when --ema_decay is set)")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -125,12 +131,19 @@ def train_args(args, total_steps):
         if not sep or not rx:
             raise ValueError(f"--lr_scale {item!r}: expected REGEX=FLOAT")
         scales.append((rx, float(val)))
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise ValueError(f"--ema_decay {args.ema_decay!r}: expected a decay in (0, 1), or 0 for no average")
     return TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
                      num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
                      no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze),
-                     skip_nonfinite=args.skip_nonfinite)
+                     skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
+
+
+def ema_eval(args):
+    """--ema_eval resolved: evaluate with the averaged weights? (unset: whenever there is an average)"""
+    return args.ema_decay > 0.0 and (args.ema_eval is None or bool(args.ema_eval))
 
 
 def run(args, batches=None):
@@ -175,7 +188,10 @@ def run(args, batches=None):
     net = DistributedDataParallel(model, device_ids=[local], output_device=local) if world > 1 else model
     opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay, num_warmup_steps=args.warmup_rate * total_steps,
                      num_training_steps=total_steps, world_size=world, param_groups=param_group_spec(model, targs),
-                     named_parameters=model.named_parameters(), skip_nonfinite=targs.skip_nonfinite)
+                     named_parameters=model.named_parameters(), skip_nonfinite=targs.skip_nonfinite,
+                     ema_decay=targs.ema_decay or None)
+    # validation and test captioning see the averaged weights (swapped in for the duration, swapped back even on an error)
+    eval_weights = opt.ema_weights if ema_eval(args) else contextlib.nullcontext
     step, t0, hist = 0, time.time(), []
 
     def check_guard():
@@ -187,6 +203,16 @@ def run(args, batches=None):
                                f"({rep['skipped']} in all); first non-finite element in {rep['first_nonfinite']} "
                                f"(arena offset {rep['offset']}).  No checkpoint was written.")
         return rep
+
+    def save(tag):
+        """<out_dir>/<experiment_name><tag>.pt: MFULL-named state_dict + optimizer/schedule/RNG (TRAIN:472 pickles the module object).
+        With --ema_decay also <experiment_name><tag>_ema.pt, the same file for inference with the average as its weights
+        (checkpoint.ema_as_model): what `utils/test_mmbart_clip_ddp.py --model_name <experiment_name><tag>_ema` decodes with."""
+        from vacnic_amd import checkpoint
+        path = os.path.join(args.out_dir, args.experiment_name + tag)
+        ck = checkpoint.save_checkpoint(path + ".pt", net, opt, step=step, rank=rank, config=dict(cfg.__dict__), vision=dict(vcfg.__dict__))
+        if opt.ema_decay is not None:
+            torch.save(checkpoint.ema_as_model(ck), path + "_ema.pt")
     plans = {}
     min_val_loss = 999.0                      # TRAIN:452
     start_step = 0
@@ -255,20 +281,21 @@ def run(args, batches=None):
             # TRAIN:455-470: validation pass per epoch; the best model and its teacher-forced outputs are kept
             vb = (synthetic.make_batch(cfg, args.val_batch_size, S=args.article_max_length, T=min(64, args.caption_max_length),
                                        seed=(int(args.seed) + 7919) % 65536, rank=0, step=i) for i in range(args.val_steps))
-            val_loss, vdict = eval_epoch(net, vb)
+            with eval_weights():
+                val_loss, vdict = eval_epoch(net, vb)
             print(json.dumps({"epoch": epoch, "validation loss": val_loss}), flush=True)
             if val_loss < min_val_loss and args.out_dir:
                 min_val_loss = val_loss
                 os.makedirs(args.out_dir, exist_ok=True)
-                from vacnic_amd import checkpoint
-                checkpoint.save_checkpoint(os.path.join(args.out_dir, args.experiment_name + ".pt"), net, opt, step=step, rank=rank, config=dict(cfg.__dict__), vision=dict(vcfg.__dict__))
+                save("")
                 with open(os.path.join(args.out_dir, args.experiment_name + "v.json"), "w") as f:
                     json.dump(vdict, f)
     if args.test_steps > 0 and rank == 0:
         # TRAIN:480-530,845-860: beam-search captions for the test split, written next to the checkpoints
         tb = (synthetic.make_batch(cfg, args.test_batch_size, S=args.article_max_length, T=min(64, args.caption_max_length),
                                    seed=(int(args.seed) + 104729) % 65536, rank=0, step=i) for i in range(args.test_steps))
-        tdict = gen_caption_from_loader_bart(net, tb, args.beam_size, args.max_length, plm_type=args.plm_type)
+        with eval_weights():
+            tdict = gen_caption_from_loader_bart(net, tb, args.beam_size, args.max_length, plm_type=args.plm_type)
         if args.out_dir:
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, args.experiment_name + ".json"), "w") as f:
@@ -279,8 +306,7 @@ def run(args, batches=None):
         check_guard()
     if rank == 0 and args.out_dir:
         os.makedirs(args.out_dir, exist_ok=True)
-        from vacnic_amd import checkpoint          # MFULL-named state_dict + optimizer/schedule/RNG (TRAIN:472 pickles the module object)
-        checkpoint.save_checkpoint(os.path.join(args.out_dir, args.experiment_name + "last.pt"), net, opt, step=step, rank=rank, config=dict(cfg.__dict__), vision=dict(vcfg.__dict__))
+        save("last")
     if world > 1:
         dist.destroy_process_group()
     return hist

@@ -160,6 +160,12 @@ AdamwGroupsArgs = _struct("vacnic_adamw_groups_args", [
     ("n", i64), ("beta1", f32), ("beta2", f32), ("eps", f32), ("grad_scale", f32),
     ("zero_grad", i32), ("clip_coef", vp)] + _GROUP_TABLE + [("skip", vp)])
 
+AdamwEmaArgs = _struct("vacnic_adamw_ema_args", [
+    ("p", vp), ("g", vp), ("m", vp), ("v", vp), ("p_bf16", vp), ("hyper", vp),
+    ("n", i64), ("beta1", f32), ("beta2", f32), ("eps", f32), ("grad_scale", f32),
+    ("zero_grad", i32), ("clip_coef", vp)] + _GROUP_TABLE + [("skip", vp), ("weight_decay", f32),
+    ("ema", vp), ("ema_decay", f32), ("ema_warmup", i32)])
+
 GradClipGroupsArgs = _struct("vacnic_grad_clip_groups_args", [
     ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("out", vp)] + _GROUP_TABLE)
 
@@ -178,7 +184,7 @@ _STRUCT_FNS = {
     "vacnic_colam_fwd": ColamFwdArgs, "vacnic_colam_bwd": ColamBwdArgs,
     "vacnic_secla_fwd": SeclaFwdArgs, "vacnic_secla_bwd": SeclaBwdArgs,
     "vacnic_name_embed_mean": NameEmbedArgs, "vacnic_adamw": AdamwArgs,
-    "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
+    "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_adamw_ema": AdamwEmaArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
     "vacnic_grad_guard": GradGuardArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
     "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs,
 }
@@ -186,6 +192,7 @@ _PLAIN_FNS = {
     "vacnic_combine_losses": [vp, vp, vp, vp, f32, f32, vp, vp],
     "vacnic_lr_step": [vp, f32, f32, f32, vp, vp],
     "vacnic_grad_clip_coef": [vp, i64, f32, f32, vp, vp, vp],
+    "vacnic_ema_swap": [vp, vp, vp, i64, vp],
     "vacnic_cast_f32_bf16": [vp, vp, i64, vp],
     "vacnic_cast_bf16_f32": [vp, vp, i64, vp],
     "vacnic_copy2d_bf16": [vp, vp, i64, i64, i64, i64, i32, vp],

@@ -54,6 +54,7 @@ class ParamArena:
         self.flat16 = torch.zeros(self.n, device=self.device, dtype=torch.bfloat16)
         self.grad = torch.zeros(self.n, device=self.device, dtype=torch.float32) if trainable else None
         self.exp_avg = self.exp_avg_sq = None
+        self.ema = None
         self.refresh_hooks = []            # callables re-deriving packed copies of weights after refresh_shadow()
         self.params = []
         for p in model.parameters():
@@ -111,6 +112,10 @@ class ParamArena:
     def init_optimizer_state(self):
         self.exp_avg = torch.zeros(self.n, device=self.device, dtype=torch.float32)
         self.exp_avg_sq = torch.zeros(self.n, device=self.device, dtype=torch.float32)
+
+    def init_ema(self):
+        """fp32 moving average of the weights (FusedAdamW(ema_decay=...)), same layout as flat32; it starts as a copy of it."""
+        self.ema = self.flat32.clone()
 
     def bucket_slices(self, bucket_bytes=256 << 20):
         """contiguous [start, end) element ranges of the gradient arena, in REVERSE layout order

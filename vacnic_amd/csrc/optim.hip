@@ -184,6 +184,84 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
   }
 }
 
+// ---- AdamW + exponential moving average of the weights (vacnic_adamw_ema, include/vacnic_hip.h) ------------------------------
+// The loop of adamw_groups_kernel with one more fp32 stream: the new p is in registers, so the average costs 4 B read + 4 B
+// written per parameter (a separate pass: 12 B and a launch).  GROUPED = false is the one-group case without the table lookup:
+// lr = hyper[0] and the struct's weight decay, which adamw_kernel<1> computes bit for bit (see adam_m / adam_v / adam_p).
+struct EmaArgs { float* __restrict__ ema; float decay; int warmup; };
+// this step's decay: torch_ema / timm warm-up over Adam's own step count t (>= 1 once vacnic_lr_step has run)
+__device__ __forceinline__ float ema_decay_at(const EmaArgs& e, float t) {
+  return e.warmup ? fminf(e.decay, (1.f + t) / (10.f + t)) : e.decay;
+}
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, bf16_t* __restrict__ pb,
+                                                        const float* __restrict__ hyper, long n4, float b1, float b2, float eps,
+                                                        float wd, float gscale, int zero_grad, const float* __restrict__ clip,
+                                                        GroupTable tab, const int64_t* __restrict__ skip, EmaArgs ea) {
+  if (skip && *skip) { skipped_step(g, n4, zero_grad); return; }      // a dropped step: the average stays too
+  const float lr0 = hyper[0], t = hyper[1];
+  if (clip) gscale *= clip[0];
+  const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
+  const float inv_sqrt_bc2 = rsqrtf(bc2);
+  const float d = ema_decay_at(ea, t), omd = 1.f - d;
+  float* __restrict__ ema = ea.ema;
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = ((f32x4*)p)[i], gv = ((f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+    f32x4 ev = ((f32x4*)ema)[i];                          // with the other four streams, ahead of the table lookup
+    const long a = tab.elem_base + (i << 2);
+    long s = 0;
+    vacnic_adamw_seg sg = {1.f, wd, 0, 0};
+    bool whole = true;
+    if (GROUPED) {
+      s = seg_of(tab, a);
+      sg = tab.seg[s];
+      whole = a + 4 <= seg_end(tab, s);
+    }
+    if (whole) {                                          // the whole vector lies in one segment
+      if (!sg.frozen) {
+        const float lr = GROUPED ? lr0 * sg.lr_scale : lr0;
+        const float step_size = lr / bc1, decay = fmaf(-lr, sg.weight_decay, 1.f);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float gr = gv[e] * gscale;
+          const float me = adam_m(b1, mv[e], gr), ve = adam_v(b2, vv[e], gr);
+          pv[e] = adam_p(pv[e], decay, step_size, me, ve, inv_sqrt_bc2, eps); mv[e] = me; vv[e] = ve;
+          ev[e] = fmaf(d, ev[e], omd * pv[e]);
+        }
+        ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv; ((f32x4*)ema)[i] = ev;
+        if (pb) ((u32x2*)pb)[i] = (u32x2){pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3])};
+      }
+    } else {                                              // a boundary inside the vector: element by element
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (a + e >= seg_end(tab, s)) { s = seg_of(tab, a + e); sg = tab.seg[s]; }
+        if (sg.frozen) continue;
+        const float lr = lr0 * sg.lr_scale;
+        const float step_size = lr / bc1, decay = fmaf(-lr, sg.weight_decay, 1.f);
+        const float gr = gv[e] * gscale;
+        const float me = adam_m(b1, mv[e], gr), ve = adam_v(b2, vv[e], gr);
+        const float pe = adam_p(pv[e], decay, step_size, me, ve, inv_sqrt_bc2, eps);
+        const long j = (i << 2) + e;
+        p[j] = pe; m[j] = me; v[j] = ve;
+        ema[j] = fmaf(d, ev[e], omd * pe);
+        if (pb) pb[j] = f2bf(pe);
+      }
+    }
+    if (zero_grad) ((f32x4*)g)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// p <-> ema by contents, shadow = bf16(new p) with cast_f32_bf16_kernel's rounding (pack2bf)
+__global__ __launch_bounds__(256) void ema_swap_kernel(float* __restrict__ p, float* __restrict__ ema, bf16_t* __restrict__ pb, long n4) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 pv = ((f32x4*)p)[i], ev = ((f32x4*)ema)[i];
+    ((f32x4*)p)[i] = ev; ((f32x4*)ema)[i] = pv;
+    if (pb) ((u32x2*)pb)[i] = (u32x2){pack2bf(ev[0], ev[1]), pack2bf(ev[2], ev[3])};
+  }
+}
+
 // grad_sumsq_kernel over the non-frozen elements: same grid, same per-thread order, same tree
 __global__ __launch_bounds__(256) void grad_sumsq_groups_kernel(const float* __restrict__ g, long n4, float gscale,
                                                                 float* __restrict__ partials, GroupTable tab) {
@@ -402,6 +480,53 @@ extern "C" int vacnic_adamw_groups(const vacnic_adamw_groups_args* a, void* stre
   const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
   hipLaunchKernelGGL(adamw_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
                      (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->grad_scale, a->zero_grad, a->clip_coef, tab, a->skip);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_adamw_ema(const vacnic_adamw_ema_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_adamw_ema, a, stream);
+  VCHECK(a && a->p && a->g && a->m && a->v && a->hyper, VACNIC_BAD_SHAPE, "adamw_ema: null operand");
+  VCHECK(a->ema, VACNIC_BAD_SHAPE, "adamw_ema: null ema");
+  VCHECK(a->n >= 0 && (a->n & 3) == 0, VACNIC_BAD_SHAPE, "adamw_ema: n=%ld must be a multiple of 4 (pad the arena)", (long)a->n);
+  VCHECK(a->ema_decay > 0.f && a->ema_decay < 1.f, VACNIC_BAD_SHAPE, "adamw_ema: ema_decay=%g must lie in (0, 1)", (double)a->ema_decay);
+  VCHECK(aligned16(a->p) && aligned16(a->g) && aligned16(a->m) && aligned16(a->v) && aligned16(a->ema) &&
+             (!a->p_bf16 || (((uintptr_t)a->p_bf16) & 7) == 0),
+         VACNIC_MISALIGNED, "adamw_ema: arenas must be 16-byte aligned");
+  const bool grouped = a->seg_start || a->seg || a->first_seg;
+  if (grouped) {
+    VCHECK_GROUP_TABLE(a, "adamw_ema");
+  } else {
+    VCHECK(a->elem_base >= 0, VACNIC_BAD_SHAPE, "adamw_ema: elem_base=%ld must be >= 0", (long)a->elem_base);
+  }
+  if (a->n == 0) return VACNIC_OK;
+  const long n4 = a->n >> 2;
+  unsigned blocks = 65536;                     // the launch shape of vacnic_adamw
+  const long need = (n4 + 255) / 256;
+  if (need < blocks) blocks = (unsigned)(need < 1 ? 1 : need);
+  const GroupTable tab = {a->seg_start, a->seg, a->first_seg, (long)a->nseg, (long)a->nblocks, (long)a->elem_base};
+  const EmaArgs ea = {a->ema, a->ema_decay, a->ema_warmup};
+  if (grouped)
+    hipLaunchKernelGGL(adamw_ema_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
+                       (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->weight_decay, a->grad_scale, a->zero_grad,
+                       a->clip_coef, tab, a->skip, ea);
+  else
+    hipLaunchKernelGGL(adamw_ema_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a->p, a->g, a->m, a->v,
+                       (bf16_t*)a->p_bf16, a->hyper, n4, a->beta1, a->beta2, a->eps, a->weight_decay, a->grad_scale, a->zero_grad,
+                       a->clip_coef, tab, a->skip, ea);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_ema_swap(float* p, float* ema, void* p_bf16, int64_t n, void* stream) {
+  VPLAN_REC(vacnic_ema_swap, p, ema, p_bf16, n, stream);
+  VCHECK(p && ema, VACNIC_BAD_SHAPE, "ema_swap: null operand");
+  VCHECK(n >= 0 && (n & 3) == 0, VACNIC_BAD_SHAPE, "ema_swap: n=%ld must be a multiple of 4 (pad the arena)", (long)n);
+  VCHECK(aligned16(p) && aligned16(ema) && (!p_bf16 || (((uintptr_t)p_bf16) & 7) == 0), VACNIC_MISALIGNED,
+         "ema_swap: p and ema must be 16-byte aligned, the shadow 8-byte");
+  VCHECK(p != ema, VACNIC_BAD_SHAPE, "ema_swap: p and ema are the same buffer");
+  if (n == 0) return VACNIC_OK;
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, (hipStream_t)stream, p, ema, (bf16_t*)p_bf16, (long)(n >> 2));
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

@@ -572,6 +572,27 @@ def adamw_groups(p, g, m, v, p16, hyper, n, table, elem_base=0, beta1=0.9, beta2
                 skip=_p(skip), **_group_table(table, elem_base))
 
 
+def adamw_ema(p, g, m, v, p16, hyper, n, ema, ema_decay, ema_warmup=True, table=None, elem_base=0, beta1=0.9, beta2=0.999, eps=1e-8,
+              weight_decay=0.01, grad_scale=1.0, zero_grad=True, clip_coef=None, skip=None):
+    """adamw() (table=None: `weight_decay`) or adamw_groups() (a table) that also keeps `ema`, laid out like p, in the same pass:
+    ema = d * ema + (1 - d) * p_new with d = ema_decay, under ema_warmup min(ema_decay, (1 + t) / (10 + t)) for Adam's step t.
+    Frozen segments and a skipped step leave ema as it is."""
+    assert ema.dtype == torch.float32
+    tab = _group_table(table, elem_base) if table is not None else dict(seg_start=None, seg=None, first_seg=None, nseg=0, nblocks=0,
+                                                                        elem_base=elem_base)
+    call_struct("vacnic_adamw_ema", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
+                n=n, beta1=beta1, beta2=beta2, eps=eps, grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef),
+                skip=_p(skip), weight_decay=weight_decay, ema=_p(ema), ema_decay=float(ema_decay), ema_warmup=int(bool(ema_warmup)),
+                **tab)
+
+
+def ema_swap(p, ema, p16=None):
+    """exchange the contents of p and ema (fp32, same size, a multiple of 4) and refresh the bf16 shadow p16 from the new p."""
+    assert p.dtype == torch.float32 and ema.dtype == torch.float32 and p.numel() == ema.numel()
+    assert p.is_contiguous() and ema.is_contiguous() and (p16 is None or (p16.is_contiguous() and p16.numel() == p.numel()))
+    call("vacnic_ema_swap", _p(p), _p(ema), _p(p16), p.numel(), _stream())
+
+
 def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0):
     """grad_clip_coef() over the non-frozen segments of the table."""
     if partials is None:

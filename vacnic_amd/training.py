@@ -2,6 +2,7 @@
 host syncs: ViT features -> multimodal BART (+ fused lm_head/CE) -> frozen guide BART -> CoLaM ->
 SECLA -> backward -> DDP all-reduce -> fused AdamW with on-device linear-warmup schedule.
 """
+import contextlib
 from dataclasses import dataclass
 
 import torch
@@ -36,6 +37,7 @@ class TrainArgs:
     lr_scale: tuple = ()                  # --lr_scale REGEX=FLOAT (repeatable): ((regex, multiple of the scheduled lr), ...)
     freeze: tuple = ()                    # --freeze REGEX (repeatable)
     skip_nonfinite: bool = False          # --skip_nonfinite: drop a step whose reduced gradient is not finite (FusedAdamW)
+    ema_decay: float = 0.0                # --ema_decay: moving average of the weights inside the AdamW step (FusedAdamW); 0 = off
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -55,8 +57,14 @@ class FusedAdamW:
     gradient arena: one lr kernel + one AdamW kernel per step, lr and step counter in device memory."""
 
     def __init__(self, arena, lr, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, num_warmup_steps=0.0,
-                 num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None, skip_nonfinite=False):
-        """skip_nonfinite: a step whose gradient (averaged over the ranks, frozen parameters left out) holds a NaN or an Inf, or
+                 num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None, skip_nonfinite=False,
+                 ema_decay=None, ema_warmup=True):
+        """ema_decay: a decay in (0, 1) keeps arena.ema, an fp32 exponential moving average of the weights, updated by the AdamW
+        kernel itself (K.adamw_ema: the new weight is in registers there): ema = d ema + (1 - d) p after every applied step, with
+        d = ema_decay, or under ema_warmup (default) min(ema_decay, (1 + t) / (10 + t)) for Adam's step count t.  It starts as a
+        copy of the weights; frozen parameters and dropped steps leave it alone.  swap_ema() / ema_weights() put it in the weights'
+        place for evaluation.  None (default): no average, the launches of before.
+        skip_nonfinite: a step whose gradient (averaged over the ranks, frozen parameters left out) holds a NaN or an Inf, or
         whose sum of squares overflows fp32, is dropped whole, decided on the device without a sync (K.grad_guard): p, m, v and
         the shadow stay, the gradient is zeroed, neither Adam's t nor the schedule position advances, and the step is counted
         (guard_report()).  Off (default): the launches and results of before.
@@ -65,8 +73,14 @@ class FusedAdamW:
         named_parameters=model.named_parameters() to match against.  A frozen parameter keeps p, m, v and its bf16 shadow untouched,
         its gradient is still computed by backward and zeroed by the step, and it does not count in the clip norm.
         None (default): one group, the ungrouped kernels."""
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay={ema_decay!r} must lie in (0, 1) (None: no average)")
         self.arena = arena
         arena.init_optimizer_state()
+        self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
+        self.ema_swapped = False          # the average currently sits in the weights' place (swap_ema)
+        if self.ema_decay is not None:
+            arena.init_ema()              # here, not in the first step: a launch plan replays the recorded addresses
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.warmup, self.total = float(num_warmup_steps), float(num_training_steps)
         self.world = world_size
@@ -95,6 +109,7 @@ class FusedAdamW:
         over the averaged gradient (after the 1/world scaling), as DDP hands it to clip_grad_norm_ in the reference; the
         coefficient stays in device memory and is applied where the AdamW kernel reads the gradient."""
         a = self.arena
+        self._not_swapped("step()")
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())   # also advances the dropout counter
         clip = None
         if self.skip_nonfinite:
@@ -110,7 +125,11 @@ class FusedAdamW:
                 clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
             else:
                 clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
-        if self.table is None:
+        if self.ema_decay is not None:
+            K.adamw_ema(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, a.ema, self.ema_decay, self.ema_warmup,
+                        self.table, 0, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True,
+                        clip_coef=clip, skip=self.guard)
+        elif self.table is None:
             K.adamw(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.betas[0], self.betas[1],
                     self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip, skip=self.guard)
         else:
@@ -135,12 +154,17 @@ class FusedAdamW:
         """first half of step() for a range-wise update (DistributedDataParallel.reduce_and_step): schedule + counters once."""
         if self.skip_nonfinite:
             raise RuntimeError("skip_nonfinite needs the whole reduced gradient before any range is updated: use step()")
+        self._not_swapped("begin_step()")
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())
 
     def step_range(self, start, end):
         """AdamW on arena elements [start, end) (a DDP bucket whose all-reduce has finished); begin_step() comes first."""
         a = self.arena
-        if self.table is None:
+        if self.ema_decay is not None:
+            K.adamw_ema(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end],
+                        self.hyper, end - start, a.ema[start:end], self.ema_decay, self.ema_warmup, self.table, start, self.betas[0],
+                        self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
+        elif self.table is None:
             K.adamw(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end], self.hyper,
                     end - start, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
         else:
@@ -151,8 +175,44 @@ class FusedAdamW:
     def zero_grad(self):
         pass            # fused into step(): the AdamW kernel clears the gradient arena it just consumed
 
+    # ---- moving average of the weights ------------------------------------------------------------------------------------
+    def _not_swapped(self, what):
+        if self.ema_swapped:
+            raise RuntimeError(f"{what} while the averaged weights are swapped in (ema_weights() / swap_ema()): the update would "
+                               "train the average and average the weights; swap back first")
+
+    def swap_ema(self):
+        """Exchange the weights and their average once: the CONTENTS of arena.flat32 and arena.ema, with the bf16 shadow re-derived
+        (one kernel, K.ema_swap).  Addresses stay, so Parameter.data views, launch plans and graphs keep reading the right buffers —
+        forward sees the other set of weights through the shadow and through the fp32 views alike.  A second call undoes it
+        bitwise.  The caller pairs the calls (ema_weights() does): after an odd number of them step(), save_checkpoint and
+        load_checkpoint refuse to run (ema_swapped).  While a launch plan is being recorded it raises: the swap would become part
+        of every replayed step."""
+        a = self.arena
+        if self.ema_decay is None:
+            raise RuntimeError("swap_ema(): the optimizer was built without ema_decay")
+        if K.recording():
+            raise RuntimeError("swap_ema() while a launch plan is being recorded: every replay would swap again")
+        K.ema_swap(a.flat32, a.ema, a.flat16)
+        for hook in a.refresh_hooks:      # packed copies of weights follow the shadow, as after refresh_shadow()
+            hook()
+        self.ema_swapped = not self.ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with optimizer.ema_weights():` — validation, caption generation or export with the averaged weights: swapped in on entry,
+        out on exit (also when the body raises).  step() inside it raises."""
+        self._not_swapped("ema_weights()")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
     def state_dict(self):
         sd = {"exp_avg": self.arena.exp_avg, "exp_avg_sq": self.arena.exp_avg_sq, "hyper": self.hyper}
+        if self.ema_decay is not None:
+            sd["ema"] = self.arena.ema
         if self.param_groups is not None:
             sd["param_groups"] = self.param_groups
         return sd
@@ -349,6 +409,8 @@ def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towe
     guarded = getattr(optimizer, "skip_nonfinite", False)
     if args.skip_nonfinite and not guarded:
         raise ValueError("TrainArgs.skip_nonfinite needs an optimizer built with FusedAdamW(..., skip_nonfinite=True)")
+    if args.ema_decay and getattr(optimizer, "ema_decay", None) is None:
+        raise ValueError("TrainArgs.ema_decay needs an optimizer built with FusedAdamW(..., ema_decay=...)")
     pipelined = isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None and not guarded
     streams.join_all(skip_wgrad=pipelined)   # side streams -> compute stream
     if isinstance(model, DistributedDataParallel):
