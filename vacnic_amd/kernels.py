@@ -539,37 +539,50 @@ def lr_step(hyper, base_lr, warmup, total, rng_counter=None):
     call("vacnic_lr_step", hyper.data_ptr(), base_lr, float(warmup), float(total), _p(rng_counter), _stream())
 
 
-def adamw(p, g, m, v, p16, hyper, n, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, zero_grad=True,
-          clip_coef=None, skip=None):
-    """skip: the int64 state of grad_guard() (or None): when its flag is set the step only zeroes g."""
-    call_struct("vacnic_adamw", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
-                n=n, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
-                zero_grad=int(zero_grad), clip_coef=_p(clip_coef), skip=_p(skip))
+def _adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip):
+    """the struct fields that vacnic_adamw, vacnic_adamw_groups and vacnic_adamw_ema have in common."""
+    return dict(p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper), n=n, beta1=beta1, beta2=beta2, eps=eps,
+                grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef), skip=_p(skip))
 
 
-def grad_clip_coef(g, n, max_norm, grad_scale=1.0, partials=None, out=None):
-    """clip_grad_norm_ (TRAIN:365-366) on device: returns the fp32 pair {clip coefficient, total norm}."""
+def _group_table(table, elem_base):
+    """struct fields of a device-resident parameter-group table (arena.group_table(...).to(device)); None: the null table, which
+    the entry points that take it as an option read as "ungrouped"."""
+    if table is None:
+        return dict(seg_start=None, seg=None, first_seg=None, nseg=0, nblocks=0, elem_base=elem_base)
+    return dict(seg_start=_p(table.seg_start), seg=_p(table.seg), first_seg=_p(table.first_seg), nseg=table.nseg,
+                nblocks=table.first_seg.numel(), elem_base=elem_base)
+
+
+def _norm_scratch(g, partials, out):
+    """the norm passes' scratch (1024 partial sums) and result {clip coefficient, total norm}, allocated where not given."""
     if partials is None:
         partials = torch.empty(1024, device=g.device, dtype=torch.float32)
     if out is None:
         out = torch.empty(2, device=g.device, dtype=torch.float32)
     assert g.dtype == torch.float32 and partials.numel() >= 1024 and out.numel() >= 2
+    return partials, out
+
+
+def adamw(p, g, m, v, p16, hyper, n, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, zero_grad=True,
+          clip_coef=None, skip=None):
+    """skip: the int64 state of grad_guard() (or None): when its flag is set the step only zeroes g."""
+    call_struct("vacnic_adamw", stream=_stream(), weight_decay=weight_decay,
+                **_adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip))
+
+
+def grad_clip_coef(g, n, max_norm, grad_scale=1.0, partials=None, out=None):
+    """clip_grad_norm_ (TRAIN:365-366) on device: returns the fp32 pair {clip coefficient, total norm}."""
+    partials, out = _norm_scratch(g, partials, out)
     call("vacnic_grad_clip_coef", _p(g), n, grad_scale, max_norm, _p(partials), _p(out), _stream())
     return out
-
-
-def _group_table(table, elem_base):
-    """struct fields of a device-resident parameter-group table (arena.group_table(...).to(device))."""
-    return dict(seg_start=_p(table.seg_start), seg=_p(table.seg), first_seg=_p(table.first_seg), nseg=table.nseg,
-                nblocks=table.first_seg.numel(), elem_base=elem_base)
 
 
 def adamw_groups(p, g, m, v, p16, hyper, n, table, elem_base=0, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, zero_grad=True,
                  clip_coef=None, skip=None):
     """adamw() with per-segment lr multiple / weight decay / frozen flag; p, g, m, v, p16 start at arena element elem_base."""
-    call_struct("vacnic_adamw_groups", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
-                n=n, beta1=beta1, beta2=beta2, eps=eps, grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef),
-                skip=_p(skip), **_group_table(table, elem_base))
+    call_struct("vacnic_adamw_groups", stream=_stream(), **_group_table(table, elem_base),
+                **_adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip))
 
 
 def adamw_ema(p, g, m, v, p16, hyper, n, ema, ema_decay, ema_warmup=True, table=None, elem_base=0, beta1=0.9, beta2=0.999, eps=1e-8,
@@ -578,12 +591,9 @@ def adamw_ema(p, g, m, v, p16, hyper, n, ema, ema_decay, ema_warmup=True, table=
     ema = d * ema + (1 - d) * p_new with d = ema_decay, under ema_warmup min(ema_decay, (1 + t) / (10 + t)) for Adam's step t.
     Frozen segments and a skipped step leave ema as it is."""
     assert ema.dtype == torch.float32
-    tab = _group_table(table, elem_base) if table is not None else dict(seg_start=None, seg=None, first_seg=None, nseg=0, nblocks=0,
-                                                                        elem_base=elem_base)
-    call_struct("vacnic_adamw_ema", stream=_stream(), p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper),
-                n=n, beta1=beta1, beta2=beta2, eps=eps, grad_scale=grad_scale, zero_grad=int(zero_grad), clip_coef=_p(clip_coef),
-                skip=_p(skip), weight_decay=weight_decay, ema=_p(ema), ema_decay=float(ema_decay), ema_warmup=int(bool(ema_warmup)),
-                **tab)
+    call_struct("vacnic_adamw_ema", stream=_stream(), weight_decay=weight_decay, ema=_p(ema), ema_decay=float(ema_decay),
+                ema_warmup=int(bool(ema_warmup)), **_group_table(table, elem_base),
+                **_adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip))
 
 
 def ema_swap(p, ema, p16=None):
@@ -595,11 +605,7 @@ def ema_swap(p, ema, p16=None):
 
 def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0):
     """grad_clip_coef() over the non-frozen segments of the table."""
-    if partials is None:
-        partials = torch.empty(1024, device=g.device, dtype=torch.float32)
-    if out is None:
-        out = torch.empty(2, device=g.device, dtype=torch.float32)
-    assert g.dtype == torch.float32 and partials.numel() >= 1024 and out.numel() >= 2
+    partials, out = _norm_scratch(g, partials, out)
     call_struct("vacnic_grad_clip_coef_groups", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=max_norm,
                 partials=_p(partials), out=_p(out), **_group_table(table, elem_base))
     return out
@@ -616,21 +622,15 @@ def grad_guard(g, n, hyper, state=None, max_norm=0.0, table=None, grad_scale=1.0
     norm} as grad_clip_coef[_groups] does (max_norm <= 0: coefficient 1), the verdict and counters into `state`, and on a skip takes
     lr_step's increment of hyper[1] back.  table: a parameter-group table (frozen segments are left out) or None.
     Returns (out, state)."""
-    dev = g.device
     if state is None:
-        state = guard_state(dev)
-    if partials is None:
-        partials = torch.empty(1024, device=dev, dtype=torch.float32)
+        state = guard_state(g.device)
     if first_idx is None:
-        first_idx = torch.empty(1024, device=dev, dtype=torch.int64)
-    if out is None:
-        out = torch.empty(2, device=dev, dtype=torch.float32)
-    assert g.dtype == torch.float32 and partials.numel() >= 1024 and out.numel() >= 2
+        first_idx = torch.empty(1024, device=g.device, dtype=torch.int64)
+    partials, out = _norm_scratch(g, partials, out)
     assert first_idx.dtype == torch.int64 and first_idx.numel() >= 1024 and state.dtype == torch.int64 and state.numel() >= 4
-    tab = _group_table(table, elem_base) if table is not None else dict(seg_start=None, seg=None, first_seg=None, nseg=0, nblocks=0,
-                                                                        elem_base=elem_base)
     call_struct("vacnic_grad_guard", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=float(max_norm),
-                partials=_p(partials), first_idx=_p(first_idx), out=_p(out), state=_p(state), hyper=_p(hyper), **tab)
+                partials=_p(partials), first_idx=_p(first_idx), out=_p(out), state=_p(state), hyper=_p(hyper),
+                **_group_table(table, elem_base))
     return out, state
 
 

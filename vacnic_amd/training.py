@@ -125,16 +125,21 @@ class FusedAdamW:
                 clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
             else:
                 clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
+        self._update(0, a.n, clip, self.guard)
+
+    def _update(self, start, end, clip, skip):
+        """the AdamW launch over arena elements [start, end): the one place that chooses among the three entry points."""
+        a = self.arena
+        r = slice(start, end)
+        bufs = (a.flat32[r], a.grad[r], a.exp_avg[r], a.exp_avg_sq[r], a.flat16[r], self.hyper, end - start)
+        kw = dict(beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, grad_scale=1.0 / self.world, zero_grad=True,
+                  clip_coef=clip, skip=skip)
         if self.ema_decay is not None:
-            K.adamw_ema(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, a.ema, self.ema_decay, self.ema_warmup,
-                        self.table, 0, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True,
-                        clip_coef=clip, skip=self.guard)
+            K.adamw_ema(*bufs, a.ema[r], self.ema_decay, self.ema_warmup, self.table, start, weight_decay=self.wd, **kw)
         elif self.table is None:
-            K.adamw(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.betas[0], self.betas[1],
-                    self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip, skip=self.guard)
+            K.adamw(*bufs, weight_decay=self.wd, **kw)
         else:
-            K.adamw_groups(a.flat32, a.grad, a.exp_avg, a.exp_avg_sq, a.flat16, self.hyper, a.n, self.table, 0, self.betas[0],
-                           self.betas[1], self.eps, grad_scale=1.0 / self.world, zero_grad=True, clip_coef=clip, skip=self.guard)
+            K.adamw_groups(*bufs, self.table, start, **kw)
 
     def guard_report(self, named_parameters=None):
         """The one method of the guard that synchronises (a 32-byte read): {"skipped": steps dropped so far, "in_a_row": current
@@ -159,18 +164,7 @@ class FusedAdamW:
 
     def step_range(self, start, end):
         """AdamW on arena elements [start, end) (a DDP bucket whose all-reduce has finished); begin_step() comes first."""
-        a = self.arena
-        if self.ema_decay is not None:
-            K.adamw_ema(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end],
-                        self.hyper, end - start, a.ema[start:end], self.ema_decay, self.ema_warmup, self.table, start, self.betas[0],
-                        self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
-        elif self.table is None:
-            K.adamw(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end], self.hyper,
-                    end - start, self.betas[0], self.betas[1], self.eps, self.wd, grad_scale=1.0 / self.world, zero_grad=True)
-        else:
-            K.adamw_groups(a.flat32[start:end], a.grad[start:end], a.exp_avg[start:end], a.exp_avg_sq[start:end], a.flat16[start:end],
-                           self.hyper, end - start, self.table, start, self.betas[0], self.betas[1], self.eps,
-                           grad_scale=1.0 / self.world, zero_grad=True)
+        self._update(start, end, None, None)
 
     def zero_grad(self):
         pass            # fused into step(): the AdamW kernel clears the gradient arena it just consumed
