@@ -430,6 +430,50 @@ typedef struct {
   int64_t nseg, nblocks, elem_base;
 } vacnic_grad_guard_args;
 int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream);
+/*
+ * Per-parameter gradient and weight statistics (what wandb.watch(model), TRAIN:456, reports per parameter), computed on the device
+ * and GATED on the device: no host sync, no allocation, recordable in a launch plan and capturable in a hipGraph like
+ * vacnic_grad_guard.  Call it after vacnic_lr_step (and after vacnic_grad_guard when there is one) and BEFORE vacnic_adamw*, which
+ * zeroes g.
+ * Layout tables, built once on the host (vacnic_amd.arena.stats_table) and resident in device memory:
+ *   a SLOT is the element range of one parameter in the arena; slots ascend, are disjoint, and may start and end on ANY element
+ *   (members of a fused group are adjacent and unaligned).  Alignment gaps, padded rows and the arena's tail lie in no slot and
+ *   are never read into a result.  Every slot is cut into UNITS of at most 4096 elements; a unit never crosses a slot.
+ *   unit_off   int64 [nunit]       arena offset of the unit's first element, ascending
+ *   unit_len   int32 [nunit]       its length, 0..4096
+ *   slot_unit  int64 [nslot + 1]   slot s owns the contiguous run of units [slot_unit[s], slot_unit[s + 1])
+ *   Offsets are clamped into [0, n], lengths to 4096 and to n, unit indices into [0, nunit]: a malformed table gives wrong
+ *   values, never an access outside [0, n) of g and p or outside the workspace.
+ * Values: x = g * grad_scale in fp32; an element is NON-FINITE exactly as the guard defines it: x * x in fp32 is NaN or Inf.
+ *   out_f  float [nslot][4]   [0] sum of x^2 over the slot's finite elements   [1] max |x| over them
+ *                             [2] sum of p^2 over the slot                     [3] max |p| over the slot    (p NULL: both 0)
+ *   out_i  int64 [nslot][2]   [0] number of non-finite elements (left out of out_f[.][0..1])   [1] number of elements with g == 0
+ * Two passes, no float atomics; two launches on the same inputs give bitwise equal outputs, whatever the workspace held before:
+ *   pass 1  one wave per unit (a fixed grid of waves striding over the units): a lane adds at most 64 terms in rising order, the
+ *           unit's head and tail up to 16-byte alignment are scalar loads, the body 16-byte vector loads; the unit's partial result
+ *           goes to the workspace (vacnic_param_stats_workspace_bytes(nunit, nslot) bytes, 16-byte aligned, owned by the caller)
+ *   pass 2  one workgroup per slot folds the slot's run of partials in unit order (a thread takes every 256th) through a fixed tree
+ * Gate, evaluated by both passes from the same device values:
+ *   hyper  float[2] (may be NULL), hyper[1] = the step count after vacnic_lr_step: the 1-based number of this step
+ *   every  >= 1;   skip  (may be NULL) the guard's state
+ *   the call FIRES when hyper == NULL, or (int64)hyper[1] % every == 0, or skip != NULL && *skip != 0 — a dropped step always records
+ *   its statistics (its hyper[1] is the count after the guard took the increment back).
+ *   Not fired: nothing is written to out_f, out_i or stamp.
+ *   Fired:     stamp int64[4] = {fires so far (incremented), (int64)hyper[1] as read (-1 if NULL), 1 if *skip != 0 else 0, 0};
+ *              the caller zeroes stamp once.
+ * Status 1..3 with a message, before any launch, for: a null g / table / workspace / output, n < 0, nslot < 1, nunit < 1,
+ * every < 1, a workspace that is too small, misaligned operands.
+ */
+typedef struct {
+  const float* g; const float* p; int64_t n; float grad_scale;
+  const int64_t* unit_off; const int32_t* unit_len; int64_t nunit;
+  const int64_t* slot_unit; int64_t nslot;
+  const float* hyper; int32_t every; const int64_t* skip;
+  void* workspace; int64_t workspace_bytes;
+  float* out_f; int64_t* out_i; int64_t* stamp;
+} vacnic_param_stats_args;
+int vacnic_param_stats(const vacnic_param_stats_args* a, void* stream);
+int64_t vacnic_param_stats_workspace_bytes(int64_t nunit, int64_t nslot);
 /* get_linear_schedule_with_warmup on device (TRAIN:99-107): hyper[0] <- base_lr*lambda(k), hyper[1] <- k+1
  * where k = hyper[1] on entry = optimizer steps already taken.  Also increments *rng_counter (the device-side
  * dropout counter, may be NULL).  Call once before vacnic_adamw. */

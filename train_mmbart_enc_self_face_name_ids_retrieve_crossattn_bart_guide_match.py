@@ -100,6 +100,11 @@ parser.add_argument("--ema_decay", type=float, default=0.0, help="exponential mo
                     "0.999), updated inside the fused AdamW step and stored in the checkpoints; 0 = off")
 parser.add_argument("--ema_eval", default=None, type=_b, help="validation and test captioning run with the averaged weights "
                     "(default: True when --ema_decay is set)")
+# per-parameter gradient / weight statistics of the optimizer (FusedAdamW(grad_stats_every=N)); off by default
+parser.add_argument("--grad_stats_every", type=int, default=0, help="every N optimizer steps (and on every step --skip_nonfinite "
+                    "drops) record each parameter's gradient norm, largest gradient, weight norm, largest weight and its non-finite "
+                    "and zero gradient elements, on the device; read at --log_every into the log record and, with --out_dir, into "
+                    "<experiment_name>_gradstats.jsonl; 0 = off")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -133,12 +138,14 @@ def train_args(args, total_steps):
         scales.append((rx, float(val)))
     if not 0.0 <= args.ema_decay < 1.0:
         raise ValueError(f"--ema_decay {args.ema_decay!r}: expected a decay in (0, 1), or 0 for no average")
+    if args.grad_stats_every < 0:
+        raise ValueError(f"--grad_stats_every {args.grad_stats_every!r}: expected a number of steps >= 1, or 0 for none")
     return TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
                      num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
                      no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze),
-                     skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay)
+                     skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay, grad_stats_every=args.grad_stats_every)
 
 
 def ema_eval(args):
@@ -189,7 +196,8 @@ def run(args, batches=None):
     opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay, num_warmup_steps=args.warmup_rate * total_steps,
                      num_training_steps=total_steps, world_size=world, param_groups=param_group_spec(model, targs),
                      named_parameters=model.named_parameters(), skip_nonfinite=targs.skip_nonfinite,
-                     ema_decay=targs.ema_decay or None)
+                     ema_decay=targs.ema_decay or None, grad_stats_every=targs.grad_stats_every)
+    stats_seen = 0                            # records of opt.grad_stats() already logged (rank 0)
     # validation and test captioning see the averaged weights (swapped in for the duration, swapped back even on an error)
     eval_weights = opt.ema_weights if ema_eval(args) else contextlib.nullcontext
     step, t0, hist = 0, time.time(), []
@@ -273,6 +281,19 @@ def run(args, batches=None):
                 if rep is not None:
                     rec["skipped"] = rep["skipped"]
                     rec["grad_norm"] = float(opt.clip[1].item())
+                if targs.grad_stats_every:
+                    # rank 0 alone reads (every rank holds the same numbers, and nothing in the step depends on them)
+                    st = opt.grad_stats(model.named_parameters())
+                    if st["fires"] > stats_seen:
+                        stats_seen = st["fires"]
+                        rec["grad_norm"], rec["grad_stats_step"] = st["total_grad_norm"], st["step"]
+                        if args.out_dir:
+                            os.makedirs(args.out_dir, exist_ok=True)
+                            keys = ("grad_norm", "grad_absmax", "weight_norm", "weight_absmax", "nonfinite", "zeros")
+                            line = {"step": st["step"], "dropped": st["dropped"], "total_grad_norm": st["total_grad_norm"],
+                                    "params": {nm: [v[k] for k in keys] for nm, v in st["params"].items()}}
+                            with open(os.path.join(args.out_dir, args.experiment_name + "_gradstats.jsonl"), "a") as f:
+                                f.write(json.dumps(line) + "\n")
                 hist.append(rec)
                 print(json.dumps(rec), flush=True)
         if targs.skip_nonfinite and args.val_steps > 0:

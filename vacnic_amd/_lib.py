@@ -173,6 +173,11 @@ GradGuardArgs = _struct("vacnic_grad_guard_args", [
     ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("first_idx", vp), ("out", vp), ("state", vp),
     ("hyper", vp)] + _GROUP_TABLE)
 
+ParamStatsArgs = _struct("vacnic_param_stats_args", [
+    ("g", vp), ("p", vp), ("n", i64), ("grad_scale", f32), ("unit_off", vp), ("unit_len", vp), ("nunit", i64),
+    ("slot_unit", vp), ("nslot", i64), ("hyper", vp), ("every", i32), ("skip", vp), ("workspace", vp), ("workspace_bytes", i64),
+    ("out_f", vp), ("out_i", vp), ("stamp", vp)])
+
 # symbol -> argtypes.  EVERY function include/vacnic_hip.h declares must appear here
 # (tests/test_abi.py parses the header and checks both directions).
 _STRUCT_FNS = {
@@ -185,7 +190,7 @@ _STRUCT_FNS = {
     "vacnic_secla_fwd": SeclaFwdArgs, "vacnic_secla_bwd": SeclaBwdArgs,
     "vacnic_name_embed_mean": NameEmbedArgs, "vacnic_adamw": AdamwArgs,
     "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_adamw_ema": AdamwEmaArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
-    "vacnic_grad_guard": GradGuardArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
+    "vacnic_grad_guard": GradGuardArgs, "vacnic_param_stats": ParamStatsArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
     "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs,
 }
 _PLAIN_FNS = {
@@ -228,7 +233,8 @@ _PLAIN_FNS = {
 EXPORTED = sorted(list(_STRUCT_FNS) + list(_PLAIN_FNS) + ["vacnic_last_error_string", "vacnic_version", "vacnic_decoder_step_sync_bytes", "vacnic_decoder_step_slots_bytes",
                                                             "vacnic_plan_begin", "vacnic_plan_size", "vacnic_plan_mark",
                                                             "vacnic_gemm_workspace_bytes", "vacnic_gemm_counters", "vacnic_comm_init",
-                                                            "vacnic_lmhead_topk_workspace", "vacnic_lmhead_topk_supported"])
+                                                            "vacnic_lmhead_topk_workspace", "vacnic_lmhead_topk_supported",
+                                                            "vacnic_param_stats_workspace_bytes"])
 
 for _name, _st in _STRUCT_FNS.items():
     _fn = getattr(lib, _name)          # AttributeError here = stale .so: fail loudly
@@ -256,6 +262,8 @@ lib.vacnic_lmhead_topk_workspace.restype = C.c_int64
 lib.vacnic_lmhead_topk_workspace.argtypes = [C.c_int64, C.c_int64, C.c_int32]
 lib.vacnic_lmhead_topk_supported.restype = C.c_int32
 lib.vacnic_lmhead_topk_supported.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+lib.vacnic_param_stats_workspace_bytes.restype = C.c_int64
+lib.vacnic_param_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
 lib.vacnic_gemm_workspace_bytes.restype = C.c_int64
 lib.vacnic_gemm_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
 lib.vacnic_gemm_counters.restype = C.c_int64

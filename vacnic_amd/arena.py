@@ -297,6 +297,54 @@ def group_table(arena, named_params, spec, default_wd):
     return table_from_segments(arena.n, [(o, *v) for o, v in slots])
 
 
+# ---- per-parameter statistics ----------------------------------------------------------------------------------------------
+STATS_UNIT = 4096   # elements per unit of the statistics kernel's first pass (include/vacnic_hip.h, vacnic_param_stats)
+
+
+class StatsTable:
+    """the tensors vacnic_param_stats reads (include/vacnic_hip.h), on the host until .to(device), and the slots they were cut
+    from: slots[s] = (offset, numel) in rising offset order; slot s owns units [slot_unit[s], slot_unit[s + 1])."""
+
+    def __init__(self, slots, unit_off, unit_len, slot_unit):
+        self.slots = slots
+        self.unit_off, self.unit_len, self.slot_unit = unit_off, unit_len, slot_unit
+        self.nslot, self.nunit = len(slots), unit_off.numel()
+
+    def to(self, device):
+        return StatsTable(self.slots, self.unit_off.to(device), self.unit_len.to(device), self.slot_unit.to(device))
+
+
+def stats_table_from_slots(slots, unit=STATS_UNIT):
+    """StatsTable from [(offset, numel)]: sorted by offset, which must leave the slots disjoint; every slot is cut into units of at
+    most `unit` (<= 4096) elements, none of which crosses a slot.  Gaps between slots lie in no unit."""
+    if not 1 <= int(unit) <= STATS_UNIT:
+        raise ValueError(f"stats table: unit={unit!r} must lie in [1, {STATS_UNIT}]")
+    slots = sorted((int(o), int(n)) for o, n in slots)
+    if not slots:
+        raise ValueError("stats table: no slots")
+    end = 0
+    unit_off, unit_len, slot_unit = [], [], [0]
+    for o, n in slots:
+        if o < end or n < 0:
+            raise ValueError(f"stats table: slot ({o}, {n}) overlaps its predecessor, which ends at {end}")
+        end = o + n
+        for u in range(o, end, unit):
+            unit_off.append(u)
+            unit_len.append(min(unit, end - u))
+        slot_unit.append(len(unit_off))
+    if not unit_off:
+        raise ValueError("stats table: every slot is empty")
+    return StatsTable(slots, torch.tensor(unit_off, dtype=torch.int64), torch.tensor(unit_len, dtype=torch.int32),
+                      torch.tensor(slot_unit, dtype=torch.int64))
+
+
+def stats_table(arena, unit=STATS_UNIT):
+    """The statistics kernel's view of the arena: one slot (offset, numel) per parameter — a parameter reachable under several names
+    has one —, without alignment gaps, pad_rows padding or the tail.  Names are not part of it: first_names() gives them when a
+    report is read.  Pure host logic: works on a "cpu" arena; the optimizer uploads the result once."""
+    return stats_table_from_slots([(o, n) for o, n, _ in arena.slots.values()], unit)
+
+
 def no_decay_spec(model):
     """[{"match": [names], "weight_decay": 0.0}] for every `.bias` and every parameter of an nn.LayerNorm — chosen by module type
     and attribute, not by name pattern (BART's LayerNorms are `*_layer_norm` and `layernorm_embedding*`).  The frozen CLIP tower

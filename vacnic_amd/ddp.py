@@ -358,8 +358,11 @@ class DistributedDataParallel(torch.nn.Module):
         embedding tables: ~1 GB of fp32 gradients that cannot overlap with backward) are still on the links while the
         optimizer's ~5.5 ms of HBM traffic for the other ~2.5 GB runs, instead of after them.  With gradient clipping the global
         norm needs every bucket first: plain reduce, then one step; so does the non-finite guard (FusedAdamW(skip_nonfinite=True)),
-        whose verdict rests on the whole all-reduced gradient — the same on every rank, which therefore take the same decision."""
-        if not self.active or clip_norm is not None or getattr(optimizer, "skip_nonfinite", False):
+        whose verdict rests on the whole all-reduced gradient — the same on every rank, which therefore take the same decision —
+        and the per-parameter statistics (FusedAdamW(grad_stats_every=N)), which read the whole averaged gradient before any range
+        of it is zeroed: every rank then records the same numbers, at the price of the bucket-wise overlap while the option is on."""
+        if (not self.active or clip_norm is not None or getattr(optimizer, "skip_nonfinite", False)
+                or getattr(optimizer, "grad_stats_every", 0)):
             self.reduce_gradients()
             optimizer.step(clip_norm=clip_norm)
             return

@@ -634,6 +634,37 @@ def grad_guard(g, n, hyper, state=None, max_norm=0.0, table=None, grad_scale=1.0
     return out, state
 
 
+def param_stats_workspace(table, device):
+    """the caller-owned scratch of param_stats() for this table (the unit partials of pass 1)."""
+    nbytes = int(_lib.lib.vacnic_param_stats_workspace_bytes(table.nunit, table.nslot))
+    return torch.empty(nbytes, device=device, dtype=torch.uint8)
+
+
+def param_stats(g, p, n, table, hyper=None, every=1, skip=None, grad_scale=1.0, workspace=None, out_f=None, out_i=None, stamp=None):
+    """Per-slot statistics of the gradient arena g (and the weights p, or None) on device, gated on device (no sync): fires when
+    hyper is None, when int(hyper[1]) % every == 0, or when skip (grad_guard's state) is set; otherwise nothing is written.
+    table: arena.stats_table(...).to(device).  out_f float[nslot][4] = {sum x^2, max |x| over finite x = g * grad_scale, sum p^2,
+    max |p|}, out_i int64[nslot][2] = {non-finite elements, elements with g == 0}, stamp int64[4] = {fires so far, hyper[1] as
+    read, fired on a skip, 0}; allocated (zeroed) where not given.  Returns (out_f, out_i, stamp)."""
+    if workspace is None:
+        workspace = param_stats_workspace(table, g.device)
+    if out_f is None:
+        out_f = torch.zeros(table.nslot, 4, device=g.device, dtype=torch.float32)
+    if out_i is None:
+        out_i = torch.zeros(table.nslot, 2, device=g.device, dtype=torch.int64)
+    if stamp is None:
+        stamp = torch.zeros(4, device=g.device, dtype=torch.int64)
+    assert g.dtype == torch.float32 and (p is None or p.dtype == torch.float32)
+    assert out_f.dtype == torch.float32 and out_f.numel() >= 4 * table.nslot and out_f.is_contiguous()
+    assert out_i.dtype == torch.int64 and out_i.numel() >= 2 * table.nslot and out_i.is_contiguous()
+    assert stamp.dtype == torch.int64 and stamp.numel() >= 4
+    call_struct("vacnic_param_stats", stream=_stream(), g=_p(g), p=_p(p), n=n, grad_scale=grad_scale, unit_off=_p(table.unit_off),
+                unit_len=_p(table.unit_len), nunit=table.nunit, slot_unit=_p(table.slot_unit), nslot=table.nslot, hyper=_p(hyper),
+                every=int(every), skip=_p(skip), workspace=_p(workspace), workspace_bytes=workspace.numel() * workspace.element_size(),
+                out_f=_p(out_f), out_i=_p(out_i), stamp=_p(stamp))
+    return out_f, out_i, stamp
+
+
 # ------------------------------------------------------------------------------------------------- misc
 def cast_f32_bf16(src, dst=None):
     if dst is None:

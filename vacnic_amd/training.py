@@ -38,6 +38,7 @@ class TrainArgs:
     freeze: tuple = ()                    # --freeze REGEX (repeatable)
     skip_nonfinite: bool = False          # --skip_nonfinite: drop a step whose reduced gradient is not finite (FusedAdamW)
     ema_decay: float = 0.0                # --ema_decay: moving average of the weights inside the AdamW step (FusedAdamW); 0 = off
+    grad_stats_every: int = 0             # --grad_stats_every N: per-parameter gradient / weight statistics every N steps (FusedAdamW)
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -58,8 +59,13 @@ class FusedAdamW:
 
     def __init__(self, arena, lr, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, num_warmup_steps=0.0,
                  num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None, skip_nonfinite=False,
-                 ema_decay=None, ema_warmup=True):
-        """ema_decay: a decay in (0, 1) keeps arena.ema, an fp32 exponential moving average of the weights, updated by the AdamW
+                 ema_decay=None, ema_warmup=True, grad_stats_every=None):
+        """grad_stats_every: N >= 1 records per-parameter statistics of the averaged gradient and of the weights (K.param_stats:
+        norm and largest magnitude of both, non-finite and exactly-zero gradient elements) on every step whose 1-based count is a
+        multiple of N, and on every step the guard drops; decided on the device, so eager steps, launch plans and graphs run the
+        same launches.  grad_stats() reads the most recent record.  They do not depend on parameter groups (a frozen parameter's
+        gradient is computed and reported) and change nothing the step writes.  0 or None (default): off, the launches of before.
+        ema_decay: a decay in (0, 1) keeps arena.ema, an fp32 exponential moving average of the weights, updated by the AdamW
         kernel itself (K.adamw_ema: the new weight is in registers there): ema = d ema + (1 - d) p after every applied step, with
         d = ema_decay, or under ema_warmup (default) min(ema_decay, (1 + t) / (10 + t)) for Adam's step count t.  It starts as a
         copy of the weights; frozen parameters and dropped steps leave it alone.  swap_ema() / ema_weights() put it in the weights'
@@ -75,6 +81,8 @@ class FusedAdamW:
         None (default): one group, the ungrouped kernels."""
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError(f"FusedAdamW: ema_decay={ema_decay!r} must lie in (0, 1) (None: no average)")
+        if grad_stats_every is not None and int(grad_stats_every) < 0:
+            raise ValueError(f"FusedAdamW: grad_stats_every={grad_stats_every!r} must be >= 0 (0 or None: off)")
         self.arena = arena
         arena.init_optimizer_state()
         self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
@@ -103,6 +111,16 @@ class FusedAdamW:
             self.clip = torch.zeros(2, device=arena.device, dtype=torch.float32)
             self._clip_scratch = torch.empty(1024, device=arena.device, dtype=torch.float32)
             self._guard_scratch = torch.empty(1024, device=arena.device, dtype=torch.int64)
+        self.grad_stats_every = int(grad_stats_every or 0)
+        self._stats = None                # (table, workspace, out_f, out_i, stamp) of K.param_stats
+        if self.grad_stats_every:
+            # allocated here, not in the first step: a launch plan replays the recorded addresses
+            from .arena import stats_table
+            tab = stats_table(arena).to(arena.device)
+            self._stats = (tab, K.param_stats_workspace(tab, arena.device),
+                           torch.zeros(tab.nslot, 4, device=arena.device, dtype=torch.float32),
+                           torch.zeros(tab.nslot, 2, device=arena.device, dtype=torch.int64),
+                           torch.zeros(4, device=arena.device, dtype=torch.int64))
 
     def step(self, clip_norm=None):
         """clip_norm: max total gradient norm (torch.nn.utils.clip_grad_norm_, TRAIN:365-366) or None.  The norm is taken
@@ -125,6 +143,11 @@ class FusedAdamW:
                 clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
             else:
                 clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
+        if self._stats is not None:
+            # after the guard (its verdict fires the record of a dropped step), before the update zeroes the gradient
+            tab, work, out_f, out_i, stamp = self._stats
+            K.param_stats(a.grad, a.flat32, a.n, tab, self.hyper, self.grad_stats_every, self.guard, 1.0 / self.world, work,
+                          out_f, out_i, stamp)
         self._update(0, a.n, clip, self.guard)
 
     def _update(self, start, end, clip, skip):
@@ -155,10 +178,38 @@ class FusedAdamW:
             name = name_at(self.arena, named_parameters, first)
         return {"skipped": skipped, "in_a_row": run, "first_nonfinite": name, "offset": first}
 
+    def grad_stats(self, named_parameters):
+        """The one method of the statistics that synchronises: the most recent record as
+        {"fires": records so far, "step": the 1-based step it describes (after a dropped step: the count the guard restored),
+         "dropped": the guard dropped that step, "total_grad_norm": float64 sqrt of the sum of the slot sums,
+         "params": {first name: {"grad_norm", "grad_absmax", "weight_norm", "weight_absmax", "nonfinite", "zeros", "numel"}}}
+        over the gradient averaged over the ranks; non-finite gradient elements are counted and left out of grad_norm and
+        grad_absmax.  Names are arena.first_names(): a tied parameter appears once.  Before the first record: "fires": 0 and no
+        params."""
+        if self._stats is None:
+            raise RuntimeError("grad_stats(): the optimizer was built with grad_stats_every=0")
+        tab, _, out_f, out_i, stamp = self._stats
+        fires, t, dropped, _ = (int(x) for x in stamp.tolist())
+        out = {"fires": fires, "step": t, "dropped": bool(dropped), "total_grad_norm": 0.0, "params": {}}
+        if fires == 0:
+            return out
+        from .arena import first_names
+        f, c = out_f.double().cpu(), out_i.cpu()
+        index = {o: s for s, (o, _) in enumerate(tab.slots)}
+        for name, p in first_names(self.arena, named_parameters):
+            s = index[self.arena.slots[id(p)][0]]
+            out["params"][name] = {"grad_norm": float(f[s, 0].sqrt()), "grad_absmax": float(f[s, 1]), "weight_norm": float(f[s, 2].sqrt()),
+                                   "weight_absmax": float(f[s, 3]), "nonfinite": int(c[s, 0]), "zeros": int(c[s, 1]),
+                                   "numel": tab.slots[s][1]}
+        out["total_grad_norm"] = float(f[:, 0].sum().sqrt())
+        return out
+
     def begin_step(self):
         """first half of step() for a range-wise update (DistributedDataParallel.reduce_and_step): schedule + counters once."""
         if self.skip_nonfinite:
             raise RuntimeError("skip_nonfinite needs the whole reduced gradient before any range is updated: use step()")
+        if self.grad_stats_every:
+            raise RuntimeError("grad_stats_every needs the whole reduced gradient before any range is zeroed: use step()")
         self._not_swapped("begin_step()")
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())
 
@@ -399,13 +450,18 @@ def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towe
     clip = None if args.no_clip_norm else args.clip_norm                         # TRAIN:365-366
     # native reducer: the bucket all-reduces sit ON the weight-gradient stream, and every bucket's AdamW range waits for that
     # bucket's own event — joining the whole stream here would hold AdamW back until the LAST collective has finished
-    # (the non-finite guard, like clipping, needs the whole reduced gradient before any range is updated)
+    # (the non-finite guard and the per-parameter statistics, like clipping, need the whole reduced gradient before any range is
+    # updated)
     guarded = getattr(optimizer, "skip_nonfinite", False)
     if args.skip_nonfinite and not guarded:
         raise ValueError("TrainArgs.skip_nonfinite needs an optimizer built with FusedAdamW(..., skip_nonfinite=True)")
     if args.ema_decay and getattr(optimizer, "ema_decay", None) is None:
         raise ValueError("TrainArgs.ema_decay needs an optimizer built with FusedAdamW(..., ema_decay=...)")
-    pipelined = isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None and not guarded
+    stats = getattr(optimizer, "grad_stats_every", 0)
+    if args.grad_stats_every and not stats:
+        raise ValueError("TrainArgs.grad_stats_every needs an optimizer built with FusedAdamW(..., grad_stats_every=N)")
+    pipelined = (isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None
+                 and not guarded and not stats)
     streams.join_all(skip_wgrad=pipelined)   # side streams -> compute stream
     if isinstance(model, DistributedDataParallel):
         model.reduce_and_step(optimizer, clip)       # all-reduce tail overlapped with the optimizer of the finished buckets
