@@ -637,6 +637,9 @@ int vacnic_image_u8_normalize(const uint8_t* src, const uint8_t* flip, float* ds
  *   vacnic_lmhead_ce_dlogits  recomputes the logits of vocabulary columns [col0, col0 + ncols) and writes
  *                             dlogits = (softmax - onehot(target)) * rowp[.][1] as bf16 [R][lddl] (columns ncols..round_up(ncols,8)
  *                             are written as zeros); the caller runs the dh / dE GEMMs on the chunk and re-uses the buffer.
+ * Domain of the targets: every target lies in [0, V) or equals ignore_index; anything else is undefined on the fused path (the
+ * combine kernel only tests target != ignore_index, so an out-of-range target would read a tl[r] that no tile wrote).  The
+ * materialised pair vacnic_ce_fwd / vacnic_ce_bwd treats every target outside [0, V) as ignored.
  * Label smoothing (label_smoothing = eps in [0, 1); anything else: VACNIC_BAD_SHAPE), torch's CrossEntropyLoss(label_smoothing=eps)
  * over the V real columns:  row_loss = (1 - eps) (lse - z_t) + eps (lse - mean_j z_j),
  *                           dlogits  = (softmax - (1 - eps) onehot(target) - eps / V) * coef.

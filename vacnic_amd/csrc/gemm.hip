@@ -519,6 +519,9 @@ extern "C" int vacnic_wgrad_group(const vacnic_wgrad_job* jobs, int64_t njobs, v
 // eps (lse - mean_j z_j) and dz_j = (softmax_j - (1 - eps) [j == t] - eps / V) g / count.  The forward epilogue also keeps the sum
 // of each tile's valid logits (part_sum), the backward reads four floats per row; both are kernels of their own
 // (gemm_t256cels.hip, ce_smooth_term_kernel, ce_rowp_smooth_kernel), so eps == 0 launches exactly what it always did.
+// Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path (only `!= ignore_index` is
+// tested here, and tl[r] is written by the one tile that holds the target's column: an out-of-range target reads a tl[r] that
+// nothing wrote).  The materialised kernels of loss.hip treat every target outside [0, V) as ignored.
 namespace {
 __global__ __launch_bounds__(256) void ce_combine_kernel(const float* __restrict__ part, const float* __restrict__ tl,
                                                           const int64_t* __restrict__ targets, float* __restrict__ row_lse,

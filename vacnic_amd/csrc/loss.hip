@@ -60,13 +60,14 @@ __device__ __forceinline__ void ce_fwd_body(const void* __restrict__ logits, con
 #pragma unroll
       for (int i = 1; i < 8; ++i) cm = fmaxf(cm, v[i]);
       const float nm = fmaxf(m, cm);
-      float cs = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) cs += __expf(v[i] - nm);
       if constexpr (LS) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) zs += v[i];
       }
+      if (nm == -INFINITY) continue;              // nothing finite yet: exp(-inf - -inf) is NaN, and (m, s) = (-inf, 0) stands
+      float cs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) cs += __expf(v[i] - nm);
       s = s * __expf(m - nm) + cs;
       m = nm;
     }
@@ -74,6 +75,7 @@ __device__ __forceinline__ void ce_fwd_body(const void* __restrict__ logits, con
       const float v = ld_logit<F32>(row, j);
       if constexpr (LS) zs += v;
       const float nm = fmaxf(m, v);
+      if (nm == -INFINITY) continue;
       s = s * __expf(m - nm) + __expf(v - nm);
       m = nm;
     }
@@ -87,13 +89,14 @@ __device__ __forceinline__ void ce_fwd_body(const void* __restrict__ logits, con
       const f32x4 b = two ? ((const f32x4*)row)[c + 256] : (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       float cm = fmaxf(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])), fmaxf(fmaxf(b[0], b[1]), fmaxf(b[2], b[3])));
       const float nm = fmaxf(m, cm);
-      float cs = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) cs += __expf(a[i] - nm) + __expf(b[i] - nm);      // exp(-inf) = 0 for the absent vector
       if constexpr (LS) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) zs += a[i] + (two ? b[i] : 0.f);
       }
+      if (nm == -INFINITY) continue;
+      float cs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) cs += __expf(a[i] - nm) + __expf(b[i] - nm);      // exp(-inf) = 0 for the absent vector
       s = s * __expf(m - nm) + cs;
       m = nm;
     }
@@ -101,6 +104,7 @@ __device__ __forceinline__ void ce_fwd_body(const void* __restrict__ logits, con
       const float v = ld_logit<F32>(row, j);
       if constexpr (LS) zs += v;
       const float nm = fmaxf(m, v);
+      if (nm == -INFINITY) continue;
       s = s * __expf(m - nm) + __expf(v - nm);
       m = nm;
     }
@@ -432,7 +436,8 @@ __global__ __launch_bounds__(256) void secla_dfaces_kernel(const float* __restri
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[e] += w[u] * v[u][e];
       }
-    } else {                                        // dense column (cannot happen with arg-max routing): plain walk
+    } else {                                        // dense column: more than 1024 non-zero rows, which B * N > 1024 allows (one face
+                                                    // that wins the arg-max of every (i, n) collects B * N of them): plain walk
       for (int r = 0; r < BN; ++r) {
         const float w = wsim[(long)r * BF + jf];
         if (w != 0.f) {

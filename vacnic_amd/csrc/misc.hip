@@ -254,7 +254,8 @@ __global__ void cat2_u8_kernel(const uint8_t* __restrict__ a, const uint8_t* __r
 // out[B, na + nb] = cat(a[B, na], b[B, nb], dim 1) on bytes: the [faces ; names] key mask of MFULL:1262 (torch.cat of two masks)
 extern "C" int vacnic_cat2_u8(const uint8_t* a, const uint8_t* b, uint8_t* out, int64_t B, int64_t na, int64_t nb, void* stream) {
   VPLAN_REC(vacnic_cat2_u8, a, b, out, B, na, nb, stream);
-  VCHECK(a && b && out && B > 0 && na >= 0 && nb >= 0 && na + nb > 0, VACNIC_BAD_SHAPE, "cat2_u8: bad operand");
+  // an empty side has no address (a [B, 0] tensor's pointer is null) and is never read
+  VCHECK(out && B > 0 && na >= 0 && nb >= 0 && na + nb > 0 && (a || na == 0) && (b || nb == 0), VACNIC_BAD_SHAPE, "cat2_u8: bad operand");
   const int64_t tot = B * (na + nb);
   hipLaunchKernelGGL(cat2_u8_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, B, na, nb);
   VLAUNCH_CHECK();

@@ -440,7 +440,8 @@ def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1, label_smoothing=0.0, bi
     """fused lm_head + CrossEntropyLoss forward without logits: returns (row_lse [R], acc = {loss_sum, count}).
     label_smoothing > 0: torch's CrossEntropyLoss(label_smoothing=) — the epilogue also keeps the per-tile sums of the logits in
     `part_sum` ([R, ceil(V / 256)] f32 scratch, allocated when not given); 0.0 is the plain path and never touches it.
-    bias: optional f32 [V] (final_logits_bias)."""
+    bias: optional f32 [V] (final_logits_bias).
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
     R = h2.shape[0]
     dev = h2.device
     tiles = (V + 255) // 256
@@ -461,7 +462,8 @@ def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1, label_smoothing=0.0, bi
 
 def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0, V=None):
     """per-row operands of lmhead_ce_dlogits: [R, 2] = {lse, coef}; with label_smoothing > 0 (which needs V) [R, 4] =
-    {lse, coef, coef (1 - eps), coef eps / V}.  Pass the same label_smoothing to lmhead_ce_dlogits."""
+    {lse, coef, coef (1 - eps), coef eps / V}.  Pass the same label_smoothing to lmhead_ce_dlogits.
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
     R = row_lse.shape[0]
     if label_smoothing != 0.0:
         if V is None:
@@ -476,7 +478,8 @@ def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_
 
 
 def lmhead_ce_dlogits(h2, emb16, targets, V, rowp, dl, col0, ncols, ignore_index=1, label_smoothing=0.0, bias=None):
-    """dl[:, :round_up(ncols, 8)] = bf16 dlogits of vocabulary columns [col0, col0 + ncols) (logits recomputed on chip)."""
+    """dl[:, :round_up(ncols, 8)] = bf16 dlogits of vocabulary columns [col0, col0 + ncols) (logits recomputed on chip).
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
     if 0.0 <= label_smoothing < 1.0 and rowp.shape[-1] != (4 if label_smoothing > 0.0 else 2):   # (a bad eps is the library's to reject)
         raise ValueError(f"lmhead_ce_dlogits: rowp has {rowp.shape[-1]} floats per row; label_smoothing={label_smoothing} reads "
                          f"{4 if label_smoothing > 0.0 else 2} (build it with lmhead_ce_rowp(label_smoothing=...))")

@@ -785,7 +785,8 @@ class LmHeadCeFn(Function):
 
 
 def lm_head_ce(h, anchor, emb16_pad, egrad, targets, V, ignore_index=1, label_smoothing=0.0):
-    """label_smoothing: torch's CrossEntropyLoss(label_smoothing=); 0.0 = the plain loss, bit-identical to the path without the option."""
+    """label_smoothing: torch's CrossEntropyLoss(label_smoothing=); 0.0 = the plain loss, bit-identical to the path without the option.
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
     loss, acc = LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled(), float(label_smoothing))
     return loss, acc
 
