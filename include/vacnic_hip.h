@@ -57,7 +57,11 @@ enum { VACNIC_ACT_NONE = 0, VACNIC_ACT_GELU = 1, VACNIC_ACT_TANH = 2, VACNIC_ACT
  *                  (fused activation backward in the dgrad of the following Linear).
  *   residual       optional bf16 [M][ldo] added after the activation.
  *   out_mode       0: bf16 store, 1: f32 store, 2: f32 atomic accumulate (out += ..; split-K ok)
- *   split_k        >=1; >1 requires out_mode 2 or a workspace.
+ *   split_k        >=1; >1 requires out_mode 2 or a workspace.  Without a workspace the K slices meet in fp32 atomics, which
+ *                  carry alpha and bias only: an activation, preact, dact_src or residual is then VACNIC_UNSUPPORTED.
+ *   alignment      x, w, bias: 16 bytes.  out / preact / dact_src / residual: 16 bytes whenever ldo keeps the rows 16-byte
+ *                  aligned (bf16: ldo % 8 == 0, fp32 out: ldo % 4 == 0), a bf16 out 8 bytes when ldo % 4 == 0; any other ldo
+ *                  takes element-wise accesses.  Otherwise VACNIC_MISALIGNED.
  *   workspace      optional: with split_k > 1 the K slices meet through an ORDERED FIX-UP instead of fp32 atomics — every slice
  *                  deposits its fp32 partial tile here, the last one to arrive sums them in slice order and runs the epilogue
  *                  once — so any out_mode / activation / residual works with split_k > 1 and the result is bitwise
@@ -99,6 +103,31 @@ int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream);
 /* sizes of the split-K fix-up buffers for an M x N output (upper bounds over every tile configuration the library may pick) */
 int64_t vacnic_gemm_workspace_bytes(int64_t M, int64_t N, int64_t split_k);
 int64_t vacnic_gemm_counters(int64_t M, int64_t N);
+
+/*
+ * Dispatch plan of vacnic_gemm_bf16: what it WOULD launch for these arguments, decided by the very host code the launch path
+ * runs (argument checks included: a call vacnic_gemm_bf16 refuses is refused here with the same status).  Touches no GPU and
+ * dereferences no operand pointer.  One launch, or two when a small row remainder is cut off into a launch of its own
+ * (launch 1 then covers rows [rows[0], M) with 64-row tiles).  Never with fused activation dropout, whose mask depends on the
+ * row index inside the whole output.
+ */
+enum {
+  VACNIC_EPI_SKINNY = 0,            /* the skinny kernel's own epilogue (M <= 8) */
+  VACNIC_EPI_DIRECT = 1,            /* accumulator registers -> global (64 / 128-row tiles: bf16 out, bias + activation only) */
+  VACNIC_EPI_BF16_TRANSPOSED = 2,   /* 256-row tiles: rounded to bf16 once, transposed through LDS; <= 1 extra operand */
+  VACNIC_EPI_F32_STAGED = 3,        /* fp32 C tile staged through LDS, 8 outputs per thread (vector or element-wise) */
+  VACNIC_EPI_ATOMIC = 4             /* K slices meet in fp32 atomics: alpha and bias only */
+};
+typedef struct {
+  int32_t nlaunch;                /* 1 or 2 */
+  int32_t reserved;
+  int64_t rows[2];                /* rows of each launch */
+  int32_t tile_hint[2];           /* the kernel that runs: 8 skinny, 64 (64x128), 128 / 261 (128x128), 256 / 258 / 260 / 262 (256x256), 264 (256x128) */
+  int32_t k_slices[2];            /* effective K slices: min(split_k, ceil(K / 64)) after rounding a slice up to 64 */
+  int32_t fixup[2];               /* 1: the slices meet through the ordered fix-up workspace */
+  int32_t epilogue[2];            /* VACNIC_EPI_* */
+} vacnic_gemm_plan_out;
+int vacnic_gemm_plan(const vacnic_gemm_args* a, vacnic_gemm_plan_out* plan);
 
 /*
  * Single-token decoder step: y = epi( LayerNorm(x + residual) . W^T + bias ), M <= 8 rows (beams x batch), K = d_model <= 1024.

@@ -134,8 +134,11 @@ def test_gemm_wgrad_both_kstrided(K, M, N, K_, split):
 
 def test_gemm_row_split_dispatch(K):
     """auto dispatch cuts a small row remainder off into its own launch (ViT: M = 32*257 = 8224 = 8192 + 32); all
-    row-indexed operands (out, preact, residual, dact_src, K-strided X) must be offset consistently."""
-    M, N, K_ = 8224, 1024, 128
+    row-indexed operands (out, preact, residual, dact_src, K-strided X) must be offset consistently.  The shape is one the cost
+    model really splits (more than 256 tiles of 256 x 256 and K >= 512; tests/test_gemm_gpu.py::test_plan_row_split_shapes)."""
+    M, N, K_ = 8224, 2048, 512
+    for kw in (dict(bias=True, act="quick_gelu", preact=True, residual=True), dict(act="gelu", dact_src=True), dict(x_kstrided=True, out_mode=1)):
+        assert [l["rows"] for l in K.gemm_plan(M, N, K_, **kw)] == [8192, 32], kw
     x = rnd(M, K_, seed=1); w = rnd(N, K_, scale=0.1, seed=2); b = rnd(N, dtype=torch.float32, seed=3); res = rnd(M, N, seed=4)
     pre = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     out = K.gemm(x, w, M, N, K_, bias=b, act="quick_gelu", preact=pre, residual=res)

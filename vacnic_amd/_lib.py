@@ -41,6 +41,11 @@ GemmArgs = _struct("vacnic_gemm_args", [
     ("workspace", vp), ("workspace_bytes", i64), ("counters", vp), ("counters_len", i64),
     ("drop_p", f32), ("drop_seed", u64), ("drop_seed_dev", vp)])
 
+GemmPlanOut = _struct("vacnic_gemm_plan_out", [
+    ("nlaunch", i32), ("reserved", i32), ("rows", i64 * 2), ("tile_hint", i32 * 2), ("k_slices", i32 * 2), ("fixup", i32 * 2),
+    ("epilogue", i32 * 2)])
+EPI_NAMES = ("skinny", "direct", "bf16_transposed", "f32_staged", "atomic")      # VACNIC_EPI_*
+
 GemvLnArgs = _struct("vacnic_gemv_ln_args", [
     ("x", vp), ("residual", vp), ("gamma", vp), ("beta", vp), ("ln_out", vp), ("w", vp), ("bias", vp), ("out", vp),
     ("M", i64), ("N", i64), ("K", i64), ("ldw", i64), ("ldo", i64), ("act", i32), ("out_mode", i32), ("eps", f32)])
@@ -222,6 +227,7 @@ _PLAIN_FNS = {
     "vacnic_zero_bytes": [vp, i64, vp],
     "vacnic_beam_init": [C.POINTER(BeamState), i32, vp],
     "vacnic_wgrad_group": [C.POINTER(WgradJob), i64, vp],
+    "vacnic_gemm_plan": [C.POINTER(GemmArgs), C.POINTER(GemmPlanOut)],
     "vacnic_plan_end": [i64], "vacnic_plan_replay": [i64, i64, i64], "vacnic_plan_destroy": [i64], "vacnic_stream_fence": [vp, vp],
     "vacnic_plan_pause": [i32],
     "vacnic_ln_partial_fold": [vp, vp, vp, i64, i64, vp],

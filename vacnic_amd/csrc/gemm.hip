@@ -293,6 +293,22 @@ static double cfg_cost(const TileCfg& c, int64_t M, int64_t N, int64_t kper, int
   return (double)rounds * ((double)c.per_cu * c.bm * c.bn * (double)kper / c.eff + kFixedUnits);
 }
 
+// ---- dispatch plan ---------------------------------------------------------------------------------------------------
+// Everything the host decides about a launch lives in two functions that vacnic_gemm_bf16 and vacnic_gemm_plan share:
+// gemm_dispatch (which launches: skinny test, cost model, row split, loop of the 256 x 256 tile) and gemm_check_plan (one
+// launch: argument checks, effective K slices, kernel, EPI_F32_STAGED).  vacnic_gemm_plan reports them without touching a GPU.
+struct OnePlan {
+  int kernel;              // tile configuration that runs: 8, 64, 128, 256, 258, 260, 261, 262 or 264
+  int split, kps, zsplits; // requested split, K per slice (multiple of BK), effective slices
+  bool fix;                // slices meet through the ordered fix-up workspace
+  int debug;               // GemmP::debug (tile_hint / 1000 | VACNIC_GEMM_DEBUG | EPI_F32_STAGED)
+  unsigned drop_thr;
+  int64_t x_bytes, w_bytes;
+  int epilogue;            // VACNIC_EPI_*
+};
+struct Dispatch { int n; vacnic_gemm_args args[2]; int hint[2]; };
+
+static int gemm_check_plan(const vacnic_gemm_args* a, int tile_hint, int ce_mode, OnePlan* o);
 static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0, bool ce_smooth = false);
 
 // A/B aid for whole-step measurements on ONE box (device-to-device spread is larger than most kernel deltas):
@@ -315,15 +331,17 @@ extern "C" int64_t vacnic_gemm_counters(int64_t M, int64_t N) {
   return ((M + 63) / 64) * ((N + 127) / 128);
 }
 
-extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
-  VPLAN_REC_STRUCT(vacnic_gemm_bf16, a, stream);
+static int gemm_dispatch(const vacnic_gemm_args* a, Dispatch* d) {
   VCHECK(a && a->x && a->w && a->out, VACNIC_BAD_SHAPE, "gemm: null operand");
   VCHECK(a->M > 0 && a->N > 0 && a->K > 0, VACNIC_BAD_SHAPE, "gemm: empty problem M=%ld N=%ld K=%ld",
          (long)a->M, (long)a->N, (long)a->K);
-  if (a->tile_hint != 0) return gemm_one(a, a->tile_hint, stream);
+  d->n = 1; d->args[0] = *a;
+  if (a->tile_hint != 0) { d->hint[0] = a->tile_hint; return VACNIC_OK; }
   if (a->M <= 8 && !a->x_kstrided && !a->w_kstrided && a->split_k <= 1 && !a->preact && !a->dact_src && !a->residual && !a->xsum &&
-      (a->K & 7) == 0)
-    return gemm_one(a, 8, stream);
+      (a->K & 7) == 0) {
+    d->hint[0] = 8;
+    return VACNIC_OK;
+  }
   const int split = a->split_k < 1 ? 1 : a->split_k;
   int64_t kper = (a->K + split - 1) / split;
   kper = (kper + BK - 1) / BK * BK;
@@ -337,8 +355,11 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
   }
   // M-split: rows are independent, so a small row remainder that would open an extra (almost empty) round is cut off
   // and run as its own small launch (e.g. the ViT's M = 32*257 = 8224 = 8192 + 32)
+  // Not with fused activation dropout: its mask is a function of the element index m * N + n of the WHOLE output and the DR
+  // epilogues count rows from the launch's row 0, so a tail launch would repeat the mask of rows 0 .. rem-1 (and a forward and
+  // a dgrad launch that dispatch differently would disagree about it).  The DR tiles are 256 x 256 / 64 x 128 only in any case.
   int split_cfg = -1; int64_t m_main = 0; double split_cost = best_cost;
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < 2 && a->drop_p == 0.f; ++i) {
     const int64_t rem = a->M % kCfgs[i].bm;
     if (rem == 0 || a->M - rem < kCfgs[i].bm || (i == 0 && a->N < 256)) continue;
     const double c = cfg_cost(kCfgs[i], a->M - rem, a->N, kper, z) + cfg_cost(kCfgs[2], rem, a->N, kper, z);
@@ -348,8 +369,9 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
   // without fused dropout (profiles/gemm_8phase_tile_ab.txt: every forward shape); the ping-pong loop (hint 256) everywhere else
   const bool fwd8 = !a->x_kstrided && !a->w_kstrided && a->drop_p == 0.f;
   auto loop_of = [&](int hint) { return hint == 256 && fwd8 ? 258 : hint; };
-  if (split_cfg < 0) return gemm_one(a, loop_of(kCfgs[best].hint), stream);
-  vacnic_gemm_args main_a = *a, tail_a = *a;
+  if (split_cfg < 0) { d->hint[0] = loop_of(kCfgs[best].hint); return VACNIC_OK; }
+  vacnic_gemm_args &main_a = d->args[0], &tail_a = d->args[1];
+  tail_a = *a;
   main_a.M = m_main;
   tail_a.M = a->M - m_main;
   const int64_t xoff = a->x_kstrided ? m_main : m_main * a->ldx;
@@ -360,16 +382,45 @@ extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
   if (a->dact_src) tail_a.dact_src = (const char*)a->dact_src + m_main * a->ldo * 2;
   if (a->residual) tail_a.residual = (const char*)a->residual + m_main * a->ldo * 2;
   if (a->xsum) tail_a.xsum = a->xsum + m_main;
-  if (int e = gemm_one(&main_a, loop_of(kCfgs[split_cfg].hint), stream)) return e;
-  return gemm_one(&tail_a, kCfgs[2].hint, stream);
+  d->n = 2; d->hint[0] = loop_of(kCfgs[split_cfg].hint); d->hint[1] = kCfgs[2].hint;
+  return VACNIC_OK;
 }
 
-static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0, bool ce_smooth) {
+extern "C" int vacnic_gemm_bf16(const vacnic_gemm_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_gemm_bf16, a, stream);
+  Dispatch d;
+  if (int e = gemm_dispatch(a, &d)) return e;
+  for (int i = 0; i < d.n; ++i)
+    if (int e = gemm_one(&d.args[i], d.hint[i], stream)) return e;
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_gemm_plan(const vacnic_gemm_args* a, vacnic_gemm_plan_out* plan) {
+  VCHECK(plan, VACNIC_BAD_SHAPE, "gemm_plan: null plan");
+  *plan = vacnic_gemm_plan_out{};
+  Dispatch d;
+  if (int e = gemm_dispatch(a, &d)) return e;
+  for (int i = 0; i < d.n; ++i) {
+    OnePlan o;
+    if (int e = gemm_check_plan(&d.args[i], d.hint[i], 0, &o)) return e;
+    plan->rows[i] = d.args[i].M; plan->tile_hint[i] = o.kernel; plan->k_slices[i] = o.zsplits;
+    plan->fixup[i] = o.fix; plan->epilogue[i] = o.epilogue;
+  }
+  plan->nlaunch = d.n;
+  return VACNIC_OK;
+}
+
+
+static int gemm_check_plan(const vacnic_gemm_args* a, int tile_hint, int ce_mode, OnePlan* o) {
   VCHECK((a->ldx & 7) == 0 && (a->ldw & 7) == 0, VACNIC_MISALIGNED, "gemm: ldx/ldw must be multiples of 8");
   VCHECK(aligned16(a->x) && aligned16(a->w), VACNIC_MISALIGNED, "gemm: x/w must be 16-byte aligned");
   VCHECK(a->out_mode >= 0 && a->out_mode <= 2, VACNIC_BAD_DTYPE, "gemm: bad out_mode %d", a->out_mode);
   const int split = a->split_k < 1 ? 1 : a->split_k;
   VCHECK(split == 1 || a->out_mode == 2 || a->workspace, VACNIC_UNSUPPORTED, "gemm: split_k needs out_mode 2 or a fix-up workspace");
+  // K slices that meet in fp32 atomics add alpha * partial (+ bias, once) to `out` and nothing else: an activation, a saved
+  // pre-activation, act' or a residual cannot be applied to a partial sum (the ordered fix-up runs the whole epilogue once)
+  VCHECK(split == 1 || a->workspace || (a->act == VACNIC_ACT_NONE && !a->preact && !a->dact_src && !a->residual), VACNIC_UNSUPPORTED,
+         "gemm: split_k through fp32 atomics carries alpha and bias only (activation / preact / dact_src / residual need the fix-up workspace)");
   if (a->workspace && split > 1) {
     VCHECK(a->counters && aligned16(a->workspace), VACNIC_BAD_SHAPE, "gemm: the split-K fix-up needs `counters` and a 16-byte aligned workspace");
     VCHECK(a->workspace_bytes >= vacnic_gemm_workspace_bytes(a->M, a->N, split) && a->counters_len >= vacnic_gemm_counters(a->M, a->N), VACNIC_BAD_SHAPE,
@@ -385,13 +436,80 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
   else VCHECK(a->ldx >= ((a->K + 7) & ~7LL), VACNIC_BAD_SHAPE, "gemm: ldx < round_up(K, 8) for K-contiguous X");
   if (a->w_kstrided) VCHECK(a->ldw >= ((a->N + 7) & ~7LL), VACNIC_BAD_SHAPE, "gemm: ldw too small for K-strided W");
   else VCHECK(a->ldw >= ((a->K + 7) & ~7LL), VACNIC_BAD_SHAPE, "gemm: ldw < round_up(K, 8) for K-contiguous W");
+  // The tile epilogues access a row in 16-byte pieces (bf16: 8 elements, fp32: 4) whenever ldo keeps every row start aligned,
+  // and the register epilogue of the small tiles stores bf16 in 8-byte pieces when ldo % 4 == 0: the base must then be aligned as
+  // well.  Any other ldo takes the element-wise path.  (The skinny kernel stores single elements; the cross-entropy epilogues
+  // use these pointers for other things and check their own operands.)
+  if (tile_hint != 8 && !ce_mode) {
+    const bool row16_bf = (a->ldo & 7) == 0;
+    VCHECK(!row16_bf || (aligned16(a->preact) && aligned16(a->dact_src) && aligned16(a->residual)), VACNIC_MISALIGNED,
+           "gemm: preact / dact_src / residual must be 16-byte aligned when ldo %% 8 == 0");
+    if (a->out_mode == 0)
+      VCHECK((!row16_bf || aligned16(a->out)) && ((a->ldo & 3) != 0 || ((uintptr_t)a->out & 7) == 0), VACNIC_MISALIGNED,
+             "gemm: a bf16 out must be 16-byte aligned when ldo %% 8 == 0 and 8-byte aligned when ldo %% 4 == 0");
+    else
+      VCHECK((a->ldo & 3) != 0 || aligned16(a->out), VACNIC_MISALIGNED, "gemm: an fp32 out must be 16-byte aligned when ldo %% 4 == 0");
+  }
 
   auto span = [](int64_t rows, int64_t cols, int64_t ld) { return ((rows - 1) * ld + cols) * 2; };
   const int64_t K8 = (a->K + 7) & ~7LL;
   const int64_t xb = a->x_kstrided ? span(a->K, (a->M + 7) & ~7LL, a->ldx) : span(a->M, K8, a->ldx);
   const int64_t wb = a->w_kstrided ? span(a->K, (a->N + 7) & ~7LL, a->ldw) : span(a->N, K8, a->ldw);
   VCHECK(xb < 0x7ffffff0LL && wb < 0x7ffffff0LL, VACNIC_UNSUPPORTED, "gemm: operand larger than 2 GiB");
+  o->x_bytes = xb; o->w_bytes = wb;
 
+  o->split = split;
+  int kps = (int)((a->K + split - 1) / split);
+  kps = (kps + BK - 1) / BK * BK;               // multiple of 64: valid for both K-tile depths
+  o->kps = kps;
+  const int zsplits = (int)((a->K + kps - 1) / kps);
+  o->zsplits = zsplits;
+  o->fix = a->workspace && zsplits > 1;
+  o->drop_thr = 0;
+  if (a->drop_p != 0.f) {
+    VCHECK(a->drop_p > 0.f && a->drop_p < 1.f, VACNIC_BAD_SHAPE, "gemm: drop_p must be in [0, 1)");
+    VCHECK(a->out_mode == 0 && a->ldo == a->N && (a->N & 15) == 0 && !ce_mode && tile_hint != 8, VACNIC_UNSUPPORTED,
+           "gemm: fused activation dropout needs a contiguous bf16 output with N %% 16 == 0 (use vacnic_dropout_bf16)");
+    VCHECK((zsplits == 1 || o->fix) , VACNIC_UNSUPPORTED, "gemm: fused activation dropout with split-K needs the fix-up workspace");
+    unsigned thr = (unsigned)(a->drop_p * 256.f + 0.5f);
+    if (thr > 255) thr = 255;
+    o->drop_thr = thr;                                 // (p < 1/512 rounds to "off")
+  }
+  if (tile_hint == 8) {     // skinny-M kernel (chosen by gemm_dispatch for M <= 8, or forced by the caller)
+    VCHECK(a->M <= 8 && !a->x_kstrided && !a->w_kstrided && zsplits == 1 && !a->preact && !a->dact_src && !a->residual && !a->xsum &&
+           (a->K & 7) == 0, VACNIC_UNSUPPORTED, "gemm: the skinny kernel needs M <= 8, K-contiguous operands, K %% 8 == 0 and a plain epilogue");
+    o->kernel = 8; o->debug = 0; o->epilogue = VACNIC_EPI_SKINNY;
+    return VACNIC_OK;
+  }
+  const int force = tile_hint % 1000;
+  o->debug = tile_hint / 1000 | gemm_env_debug();
+  // dispatch of the epilogue (256-row tiles): what the bf16 transposed epilogue cannot serve takes the fp32 staged one
+  if (((a->M - 1) * a->ldo + a->N) * 2 >= 0x7ffffff0LL) o->debug |= EPI_F32_STAGED;      // it addresses its outputs through 32-bit buffer offsets
+  if ((a->preact != nullptr) + (a->dact_src != nullptr) + (a->residual != nullptr) > 1) o->debug |= EPI_F32_STAGED;   // it carries one extra operand
+  if (o->drop_thr && !a->preact && !a->dact_src) o->debug |= EPI_F32_STAGED;     // dropout rides on its saved-pre-activation / act' instances
+  // the kernel: activation dropout has DR instances of the 256 x 256, 256 x 128 and 64 x 128 tiles only; 260 / 261 / 262 are the
+  // A/B baselines kept for the ablations in profiles/ (plain K loops and the 64-wide software-pipelined loop); 258 is the
+  // 8-phase counted-wait loop (forward layout); anything else that is not 256 / 264 / 128 runs the 64 x 128 ring
+  if (o->drop_thr) o->kernel = force == 256 || force == 264 ? force : 64;
+  else if (ce_mode) o->kernel = 256;
+  else if (force == 260 || force == 261 || force == 262 || force == 264 || force == 258 || force == 256 || force == 128) o->kernel = force;
+  else o->kernel = 64;
+  VCHECK(o->kernel != 258 || (!a->x_kstrided && !a->w_kstrided), VACNIC_UNSUPPORTED,
+         "gemm: the 8-phase loop is built for the forward layout (both operands K-contiguous)");
+  // which epilogue of gemm_tile these arguments reach (the kernel tests the same conditions in this order)
+  const bool bm256 = o->kernel >= 256 && o->kernel != 261;     // 261 is a 128 x 128 tile
+  const bool plain_ops = !a->preact && !a->dact_src && !a->residual;
+  if (ce_mode) o->epilogue = VACNIC_EPI_F32_STAGED;
+  else if (!bm256 && a->out_mode == 0 && plain_ops && (a->ldo & 3) == 0 && !(o->debug & EPI_F32_STAGED) && !o->drop_thr) o->epilogue = VACNIC_EPI_DIRECT;
+  else if (bm256 && a->out_mode == 0 && (a->ldo & 7) == 0 && (a->N & 7) == 0 && !(o->debug & EPI_F32_STAGED)) o->epilogue = VACNIC_EPI_BF16_TRANSPOSED;
+  else if (a->out_mode == 2 && zsplits > 1 && !o->fix) o->epilogue = VACNIC_EPI_ATOMIC;
+  else o->epilogue = VACNIC_EPI_F32_STAGED;
+  return VACNIC_OK;
+}
+
+static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0, bool ce_smooth) {
+  OnePlan o;
+  if (int e = gemm_check_plan(a, tile_hint, ce_mode, &o)) return e;
   GemmP p;
   p.x = (const bf16_t*)a->x; p.w = (const bf16_t*)a->w; p.bias = a->bias;
   p.out = a->out; p.preact = (bf16_t*)a->preact; p.dact_src = (const bf16_t*)a->dact_src;
@@ -399,33 +517,22 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
   p.xsum = a->xsum;
   p.M = (int)a->M; p.N = (int)a->N; p.K = (int)a->K;
   p.ldx = (int)a->ldx; p.ldw = (int)a->ldw; p.ldo = (int)a->ldo;
-  p.act = a->act; p.out_mode = ce_mode ? ce_mode : a->out_mode; p.split_k = split;
+  p.act = a->act; p.out_mode = ce_mode ? ce_mode : a->out_mode;
   p.ce_col0 = ce_col0;
-  int kps = (int)((a->K + split - 1) / split);
-  kps = (kps + BK - 1) / BK * BK;               // multiple of 64: valid for both K-tile depths
-  p.k_per_split = kps;
-  const int zsplits = (int)((a->K + kps - 1) / kps);
+  p.k_per_split = o.kps;
+  const int zsplits = o.zsplits;
   p.split_k = zsplits;
   p.alpha = a->alpha;
-  p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
+  p.x_bytes = (unsigned)o.x_bytes; p.w_bytes = (unsigned)o.w_bytes;
   p.tiles_m = p.tiles_n = 0;
-  p.ws = (a->workspace && zsplits > 1) ? (float*)a->workspace : nullptr;
+  p.ws = o.fix ? (float*)a->workspace : nullptr;
   p.cnt = p.ws ? a->counters : nullptr;
-  p.drop_thr = 0; p.drop_inv = 1.f; p.drop_seed = a->drop_seed; p.drop_seed_dev = (const unsigned long long*)a->drop_seed_dev;
-  if (a->drop_p != 0.f) {
-    VCHECK(a->drop_p > 0.f && a->drop_p < 1.f, VACNIC_BAD_SHAPE, "gemm: drop_p must be in [0, 1)");
-    VCHECK(a->out_mode == 0 && a->ldo == a->N && (a->N & 15) == 0 && !ce_mode && tile_hint != 8, VACNIC_UNSUPPORTED,
-           "gemm: fused activation dropout needs a contiguous bf16 output with N %% 16 == 0 (use vacnic_dropout_bf16)");
-    VCHECK((zsplits == 1 || p.ws) , VACNIC_UNSUPPORTED, "gemm: fused activation dropout with split-K needs the fix-up workspace");
-    unsigned thr = (unsigned)(a->drop_p * 256.f + 0.5f);
-    if (thr > 255) thr = 255;
-    p.drop_thr = thr;                                  // (p < 1/512 rounds to "off")
-    p.drop_inv = 256.f / (256.f - (float)thr);
-  }
+  p.drop_thr = o.drop_thr; p.drop_inv = o.drop_thr ? 256.f / (256.f - (float)o.drop_thr) : 1.f;
+  p.drop_seed = a->drop_seed; p.drop_seed_dev = (const unsigned long long*)a->drop_seed_dev;
+  p.debug = o.debug;
   hipStream_t s = (hipStream_t)stream;
-  if (tile_hint == 8) {     // skinny-M kernel (chosen by vacnic_gemm_bf16 for M <= 8, or forced by the caller)
-    VCHECK(a->M <= 8 && !a->x_kstrided && !a->w_kstrided && zsplits == 1 && !a->preact && !a->dact_src && !a->residual && !a->xsum &&
-           (a->K & 7) == 0, VACNIC_UNSUPPORTED, "gemm: the skinny kernel needs M <= 8, K-contiguous operands, K %% 8 == 0 and a plain epilogue");
+  const bool xk = a->x_kstrided, wk = a->w_kstrided;
+  if (o.kernel == 8) {
     constexpr int CW = 4;
     dim3 grid((unsigned)((a->N + CW - 1) / CW));
     if (a->K >= 2048 && a->N <= 8192) hipLaunchKernelGGL((gemm_skinny_kernel<8, CW, 4>), grid, dim3(256), 0, s, p);   // long reduction, few columns: 4 waves split K
@@ -433,30 +540,23 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
     VLAUNCH_CHECK();
     return VACNIC_OK;
   }
-  const int force = tile_hint % 1000;
-  p.debug = tile_hint / 1000 | gemm_env_debug();
-  // dispatch of the epilogue (256-row tiles): what the bf16 transposed epilogue cannot serve takes the fp32 staged one
-  if (((a->M - 1) * a->ldo + a->N) * 2 >= 0x7ffffff0LL) p.debug |= EPI_F32_STAGED;      // it addresses its outputs through 32-bit buffer offsets
-  if ((a->preact != nullptr) + (a->dact_src != nullptr) + (a->residual != nullptr) > 1) p.debug |= EPI_F32_STAGED;   // it carries one extra operand
-  if (p.drop_thr && !a->preact && !a->dact_src) p.debug |= EPI_F32_STAGED;     // dropout rides on its saved-pre-activation / act' instances
-  const bool big = force == 256;
-  const bool mid = force == 128;
-  if (p.drop_thr) {                 // activation dropout: 256 x 256, 256 x 128 and 64 x 128 tiles carry the DR epilogues
-    if (big) return launch_t256d(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-    if (force == 264) return launch_t264d(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-    return launch_t64d(p, a->x_kstrided, a->w_kstrided, zsplits, s);
+  if (p.drop_thr) {                 // the DR epilogues
+    if (o.kernel == 256) return launch_t256d(p, xk, wk, zsplits, s);
+    if (o.kernel == 264) return launch_t264d(p, xk, wk, zsplits, s);
+    return launch_t64d(p, xk, wk, zsplits, s);
   }
-  // A/B baselines kept for the ablations in profiles/: plain K loops and the 64-wide software-pipelined loop
-  if (force == 260) return launch_t260(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-  if (force == 261) return launch_t261(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-  if (force == 262) return launch_t262(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-  if (force == 264) return launch_t264(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong, half-width tile
-  if (force == 258 && !ce_mode) return launch_t258(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // 256x256, 8-phase counted-wait loop (forward layout)
-  if (ce_mode && ce_smooth) return launch_t256cels(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // label smoothing: its own kernel
-  if (ce_mode) return launch_t256ce(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-  if (big) return launch_t256(p, a->x_kstrided, a->w_kstrided, zsplits, s);   // ping-pong loop
-  if (mid) return launch_t128(p, a->x_kstrided, a->w_kstrided, zsplits, s);
-  return launch_t64(p, a->x_kstrided, a->w_kstrided, zsplits, s);
+  if (ce_mode && ce_smooth) return launch_t256cels(p, xk, wk, zsplits, s);   // label smoothing: its own kernel
+  if (ce_mode) return launch_t256ce(p, xk, wk, zsplits, s);
+  switch (o.kernel) {
+    case 260: return launch_t260(p, xk, wk, zsplits, s);
+    case 261: return launch_t261(p, xk, wk, zsplits, s);
+    case 262: return launch_t262(p, xk, wk, zsplits, s);
+    case 264: return launch_t264(p, xk, wk, zsplits, s);   // ping-pong, half-width tile
+    case 258: return launch_t258(p, xk, wk, zsplits, s);   // 256x256, 8-phase counted-wait loop (forward layout)
+    case 256: return launch_t256(p, xk, wk, zsplits, s);   // ping-pong loop
+    case 128: return launch_t128(p, xk, wk, zsplits, s);
+    default: return launch_t64(p, xk, wk, zsplits, s);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

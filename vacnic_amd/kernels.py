@@ -5,6 +5,7 @@ path is a hand-written gfx950 kernel in libvacnic_hip.so.  All wrappers launch o
 `torch.cuda.current_stream()` so they are hipGraph-capturable, and all fail loudly on CPU tensors.
 """
 import contextlib
+import ctypes
 
 import torch
 
@@ -242,6 +243,31 @@ def gemm(x, w, M, N, K, *, bias=None, out=None, ldx=None, ldw=None, ldo=None, x_
                 counters_len=cntn or 0, drop_p=float(drop[0]) if drop else 0.0, drop_seed=int(drop[1]) if drop else 0,
                 drop_seed_dev=_p(drop[2]) if drop else None)
     return out
+
+
+def gemm_plan(M, N, K, *, x_kstrided=False, w_kstrided=False, ldx=None, ldw=None, ldo=None, act=None, out_mode=0, split_k=1, alpha=1.0,
+              bias=False, preact=False, dact_src=False, residual=False, xsum=False, tile_hint=-1, fixup=False, drop_p=0.0, ptrs=None):
+    """what gemm() would launch for this call (vacnic_gemm_plan: the launch path's own decision code, no GPU needed): a list with
+    one dict per launch, keys rows / tile_hint / k_slices / fixup / epilogue (a name from _lib.EPI_NAMES).  Operands are flags
+    (any aligned address stands in for a present one) unless `ptrs` gives addresses by name; tile_hint as in gemm(), except that
+    0 is NOT looked up in gemm_tuned.json here.  Raises what gemm() would raise."""
+    fake = 1 << 20
+    ptr = {"x": fake, "w": fake, "out": fake, "bias": fake if bias else None, "preact": fake if preact else None,
+           "dact_src": fake if dact_src else None, "residual": fake if residual else None, "xsum": fake if xsum else None}
+    ptr.update(ptrs or {})
+    ws = wsb = cnt = cntn = None
+    if fixup and split_k > 1:
+        ws, cnt = fake, fake
+        wsb, cntn = int(_lib.lib.vacnic_gemm_workspace_bytes(M, N, split_k)), int(_lib.lib.vacnic_gemm_counters(M, N))
+    a = _lib.GemmArgs(M=M, N=N, K=K, ldx=ldx if ldx is not None else (M if x_kstrided else K),
+                      ldw=ldw if ldw is not None else (N if w_kstrided else K), ldo=ldo if ldo is not None else N,
+                      x_kstrided=int(x_kstrided), w_kstrided=int(w_kstrided), act=ACT[act], out_mode=out_mode, split_k=split_k,
+                      alpha=alpha, tile_hint=max(tile_hint, 0), workspace=ws, workspace_bytes=wsb or 0, counters=cnt,
+                      counters_len=cntn or 0, drop_p=float(drop_p), drop_seed=0, drop_seed_dev=None, **ptr)
+    out = _lib.GemmPlanOut()
+    _lib.check(_lib.lib.vacnic_gemm_plan(ctypes.byref(a), ctypes.byref(out)))
+    return [dict(rows=int(out.rows[i]), tile_hint=int(out.tile_hint[i]), k_slices=int(out.k_slices[i]), fixup=bool(out.fixup[i]),
+                 epilogue=_lib.EPI_NAMES[out.epilogue[i]]) for i in range(out.nlaunch)]
 
 
 def can_fuse_dropout(N, ldo=None):
