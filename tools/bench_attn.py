@@ -24,7 +24,8 @@ def main():
     r = lambda *s: (torch.randn(*s, device="cuda") * 0.5).bfloat16()
     cnt = torch.zeros(1, device="cuda", dtype=torch.int64)
     shapes = [("enc self", 32, 16, 512, 512, False, True), ("enc cross img", 32, 16, 512, 40, False, False), ("dec self", 32, 16, 64, 64, True, False),
-              ("dec cross", 32, 16, 64, 512, False, True), ("ViT", 32, 16, 257, 257, False, False), ("cfg4 self", 32, 16, 1024, 1024, False, True)]
+              ("dec cross", 32, 16, 64, 512, False, True), ("ViT", 32, 16, 257, 257, False, False), ("cfg4 self", 32, 16, 1024, 1024, False, True),
+              ("name", 32, 16, 20, 24, False, True)]
     print(f"{'shape':14s} {'B':>3s} {'H':>3s} {'Tq':>5s} {'Tk':>5s} | fwd us (TF) | fwd+drop | bwd us (TF) | bwd+drop || every tile with one masked key (the general softmax path): fwd | bwd")
     for name, B, H, Tq, Tk, causal, masked in shapes:
         d = H * 64

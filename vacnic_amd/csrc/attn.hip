@@ -87,6 +87,7 @@ struct AttnP {
   int causal; float scale;
   // attention-probability dropout (MFULL:546): keep iff byte >= drop_thr (p quantised to 1/256), kept entries scaled by drop_inv
   unsigned drop_thr; float drop_inv; unsigned long long drop_seed; const unsigned long long* drop_seed_dev;
+  int rows16;        // backward: dq / dk / dv base pointers 16-byte aligned -> the gradients leave as whole 128-byte rows
 };
 
 // Dropout mask of the probabilities: ONE Philox4x32-10 block per 4 x 4 patch of the [Tq, Tk] matrix of a (batch, head) — 16
@@ -363,6 +364,31 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   if (qidx < p.Tq && p.lse && hh == 0) p.lse[((long)b * p.H + hd) * p.Tq + qidx] = m_run * 0.6931471805599453f + __logf(l_tot);
 }
 
+// A wave's 32 x 64 gradient tile (two 32x32 accumulators, the row on the lane) leaves as whole rows, the way the forward's output
+// does: rounded to bf16 (value * scale first) into 4 KiB of LDS owned by the wave, [32 rows][128 B] with the 16-byte chunks
+// XOR-swizzled by the row, then 128-byte row segments go out with 16-byte lanes.  Rows at or past nrows are not stored.  `dst` is
+// the element (row0, first column of the head); it, and ld, must be 16-byte aligned.
+__device__ __forceinline__ void store_rows32(char* ot, const f32x16 (&x)[2], float scale, bf16_t* dst, int ld, int row0, int nrows,
+                                             int lane) {
+  const int rl = lane & 31, hh = lane >> 5;
+#pragma unroll
+  for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const u32x2 pk = {pack2bf(x[hb][4 * g] * scale, x[hb][4 * g + 1] * scale),
+                        pack2bf(x[hb][4 * g + 2] * scale, x[hb][4 * g + 3] * scale)};
+      const int c16 = hb * 4 + g;
+      *(u32x2*)(ot + rl * 128 + ((c16 ^ (rl & 7)) << 4) + 8 * hh) = pk;
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // wave-local: written and read by the same wave
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = (lane >> 3) + 8 * i, c16 = lane & 7;
+    const u32x4 v = *(const u32x4*)(ot + row * 128 + ((c16 ^ (row & 7)) << 4));
+    if (row0 + row < nrows) *(u32x4*)(dst + (long)row * ld + c16 * 8) = v;
+  }
+}
+
 // =================================================================================================
 // delta[b][h][q] = sum_d dO[q][d] * O[q][d]
 // =================================================================================================
@@ -530,7 +556,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnP p) {
     lds_barrier();
   }
 
-  if (kidx < p.Tk) {
+  // The Q / dO ring is idle behind the loop's last barrier: each wave turns dK and dV round in 2 x 4 KiB of it (store_rows32).
+  // Unaligned dk / dv take the accumulator layout's own 8-byte pieces.
+  if (p.rows16) {
+    if (k0 < p.Tk) {
+      char* ot = smem + wave * 8192;
+      // (dV carries no scale: * 1.f is exact)
+      store_rows32(ot, dk, p.scale, p.dk + (long)b * p.bsdk + (long)k0 * p.lddk + hd * 64, p.lddk, k0, p.Tk, lane);
+      store_rows32(ot + 4096, dv, 1.f, p.dv + (long)b * p.bsdv + (long)k0 * p.lddv + hd * 64, p.lddv, k0, p.Tk, lane);
+    }
+  } else if (kidx < p.Tk) {
     bf16_t* dkrow = p.dk + (long)b * p.bsdk + (long)kidx * p.lddk + hd * 64;
     bf16_t* dvrow = p.dv + (long)b * p.bsdv + (long)kidx * p.lddv + hd * 64;
 #pragma unroll
@@ -673,7 +708,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     if (qidx < p.Tq && hh == 0) p.delta_out[((long)b * p.H + hd) * p.Tq + qidx] = dsum;
     return;
   }
-  if (qidx < p.Tq) {
+  if (p.rows16) {                                          // whole rows through the idle K/V ring, as in the dK/dV kernel
+    if (q0 < p.Tq)
+      store_rows32(smem + wave * 4096, dq, p.scale, p.dq + (long)b * p.bsdq + (long)q0 * p.lddq + hd * 64, p.lddq, q0, p.Tq, lane);
+  } else if (qidx < p.Tq) {
     bf16_t* drow = p.dq + (long)b * p.bsdq + (long)qidx * p.lddq + hd * 64;
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb)
@@ -682,6 +720,333 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
         u32x2 a = {pack2bf(dq[hb][4 * g] * p.scale, dq[hb][4 * g + 1] * p.scale), pack2bf(dq[hb][4 * g + 2] * p.scale, dq[hb][4 * g + 3] * p.scale)};
         *(u32x2*)(drow + hb * 32 + 8 * g + 4 * hh) = a;
       }
+  }
+}
+
+// =================================================================================================
+// Tq <= 64 (decoder self- and cross-attention, name attention): the whole backward of one (batch, head) in ONE workgroup —
+// delta, dK / dV and dQ in one launch instead of a delta sweep, a dK/dV launch and a dQ launch that each gave the problem
+// 128 query slots or four workgroups.  Q and dO (64 rows, zero past Tq) and the row statistics stay in LDS throughout.
+//   sweep 1 (delta): query on the lane, the DELTA_PASS body of the dQ kernel over 64-key tiles of K and V.  Only two 32-query
+//     blocks exist, so wave w takes query block w & 1 and the 32-key half w >> 1 of every tile; the two partial sums of a
+//     query meet in LDS in a fixed order.  delta also goes to delta_out.
+//   sweep 2 (gradients): key on the lane, the dK/dV kernel's body over 128-key tiles: each wave takes the K / V fragments of
+//     its 32 keys from the staged tile and forms P and dS against the resident Q / dO.  Every query is here, so dK and dV of
+//     the tile are complete when it is done and leave at once (store_rows32).  dS^T crosses LDS once as bf16
+//     [128 keys][64 queries] in the swizzled tile layout, so frag_tr hands it back as the B operand of dQ^T[d][q] += K^T dS^T; wave w owns the 32 x 32 block
+//     (d half w >> 1, query block w & 1) of dQ^T and accumulates the tile's eight 16-key steps in ascending key order.
+// LDS: Q, dO (16 KiB) | ring (32 KiB: 2 x {K, V} 64-key tiles in sweep 1, one {K, V} 128-key tile in sweep 2) | dS^T (16 KiB, also
+// the transposition space of the stores) | lse, delta, -lse log2(e), uniform probability [64 each] | delta partials [2][64] |
+// key bias of the two tiles in flight [2][64] + their flags | the waves' any-valid-key flags.
+// A batch row whose keys are ALL masked softmaxes uniformly in the forward (over every key, or the keys <= q with the causal
+// mask), but its lse is finfo.min and has absorbed log(count): exp(score - lse) cannot give the probabilities back.  The
+// workgroup sees the whole mask row, so it knows, and takes 1 / count for the masked keys instead.
+// =================================================================================================
+constexpr int SHORT_LDS = 8 * TILE_B + (256 + 128 + 128 + 8) * 4;
+
+template <bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_bwd_short_kernel(AttnP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x / p.H, hd = blockIdx.x - b * p.H;
+  const int rl = lane & 31, hh = lane >> 5;
+  const int qb = wave & 1, wh = wave >> 1;
+  const int nqb = p.Tq > 32 ? 2 : 1;                   // query blocks that hold a query
+  char* qt = smem;
+  char* dot = smem + TILE_B;
+  char* ring = smem + 2 * TILE_B;
+  char* dst = smem + 6 * TILE_B;
+  float* stats = (float*)(smem + 8 * TILE_B);
+  float* part = stats + 256;
+  float* tbias = part + 128;
+  unsigned* dirty = (unsigned*)(tbias + 128);
+  unsigned* anyvalid = dirty + 2;
+  constexpr float LOG2E = 1.4426950408889634f;
+  const float scale2 = p.scale * LOG2E;
+
+  const bf16_t* vb = p.v + (long)b * p.bsv + hd * 64;
+  __amdgpu_buffer_rsrc_t qs = make_rsrc(p.q + (long)b * p.bsq + hd * 64, p.Tq, p.ldq);
+  __amdgpu_buffer_rsrc_t ks = make_rsrc(p.k + (long)b * p.bsk + hd * 64, p.Tk, p.ldk);
+  __amdgpu_buffer_rsrc_t vs = make_rsrc(vb, p.Tk, p.ldv);
+  __amdgpu_buffer_rsrc_t dos = make_rsrc(p.dout + (long)b * p.bso + hd * 64, p.Tq, p.ldo);
+  const uint8_t* mrow = p.key_mask ? p.key_mask + (long)b * p.Tk : nullptr;
+  auto key_bias = [&](int key) -> float {              // 0 / FMIN (masked) / -inf (padding), as fill_key_bias
+    float v = 0.f;
+    if (key >= p.Tk) v = -INFINITY;
+    else if (mrow && mrow[key] == 0) v = FMIN;
+    return v;
+  };
+  // wave 0 holds the bias of the 64 keys of a sweep-1 tile, one per lane; the tile's flag is one ballot
+  auto put_bias = [&](int slot, float v) {
+    if (wave == 0) {
+      tbias[slot * 64 + lane] = v;
+      const unsigned long long any = __builtin_amdgcn_ballot_w64(v != 0.f);
+      if (lane == 0) dirty[slot] = any != 0ull;
+    }
+  };
+  DropCtx dctx;
+  if (DROP) dctx = drop_ctx(p, b, hd);
+
+  // ---------------------------------------------------------------------------------------------- sweep 1: delta
+  int ntile = (p.Tk + 63) >> 6;
+  if (p.causal) ntile = min(ntile, (p.Tq + 63) >> 6);
+  {
+    float b0 = 0.f, l0 = INFINITY;
+    bool valid = mrow == nullptr;
+    if (mrow)
+      for (int j = tid; j < p.Tk; j += 256) valid |= mrow[j] != 0;
+    if (wave == 0) {
+      b0 = key_bias(lane);
+      if (lane < p.Tq) l0 = p.lse[((long)b * p.H + hd) * p.Tq + lane];
+    }
+    stage64(qs, qt, 0, p.Tq, p.ldq, wave, lane);
+    stage64(dos, dot, 0, p.Tq, p.ldo, wave, lane);
+    stage64(ks, ring, 0, p.Tk, p.ldk, wave, lane);
+    stage64(vs, ring + TILE_B, 0, p.Tk, p.ldv, wave, lane);
+    if (wave == 0) {
+      stats[lane] = l0; stats[128 + lane] = -l0 * LOG2E;                     // (padding queries: lse = +inf -> probability 0)
+      stats[192 + lane] = lane < p.Tq ? 1.f / (float)(p.causal ? min(lane, p.Tk - 1) + 1 : p.Tk) : 0.f;
+    }
+    {
+      const unsigned long long any = __builtin_amdgcn_ballot_w64(valid);
+      if (lane == 0) anyvalid[wave] = any != 0ull;
+    }
+    put_bias(0, b0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+  }
+  const int qidx = qb * 32 + rl;
+  float dsum = 0.f;
+  const bool allmasked = __builtin_amdgcn_readfirstlane((int)(anyvalid[0] | anyvalid[1] | anyvalid[2] | anyvalid[3])) == 0;
+  {
+    bf16x8 qf[4], dof[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { qf[s] = frag_row(qt, qb * 32, s, lane); dof[s] = frag_row(dot, qb * 32, s, lane); }
+    const float lse_q = stats[qidx], nl2 = stats[128 + qidx], uni_q = stats[192 + qidx];
+    for (int t = 0; t < ntile; ++t) {
+      const int cur = t & 1;
+      char* kt = ring + cur * (2 * TILE_B);
+      char* vt = kt + TILE_B;
+      float bn = 0.f;
+      if (t + 1 < ntile) {
+        char* nk = ring + (cur ^ 1) * (2 * TILE_B);
+        if (wave == 0) bn = key_bias((t + 1) * 64 + lane);
+        stage64(ks, nk, (t + 1) * 64, p.Tk, p.ldk, wave, lane);
+        stage64(vs, nk + TILE_B, (t + 1) * 64, p.Tk, p.ldv, wave, lane);
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      lds_barrier();
+      const bool plain = !p.causal && __builtin_amdgcn_readfirstlane((int)dirty[cur]) == 0;      // see fill_key_bias
+      if (qb < nqb) {
+        f32x16 s = (f32x16)(0.f), dp = (f32x16)(0.f);
+#pragma unroll
+        for (int ks4 = 0; ks4 < 4; ++ks4) {
+          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(kt, wh * 32, ks4, lane), qf[ks4], s, 0, 0, 0);
+          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(vt, wh * 32, ks4, lane), dof[ks4], dp, 0, 0, 0);
+        }
+        uint32_t mw[4];
+        if (DROP) drop_block_keys(dctx, qidx, t * 64 + wh * 32 + 4 * hh, lane, mw);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int kl0 = wh * 32 + 8 * g + 4 * hh;
+          float mk[4] = {1.f, 1.f, 1.f, 1.f};
+          if (DROP) drop_word_factors(dctx, mw[g], mk);
+          if (plain) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float pe = __builtin_amdgcn_exp2f(fmaf(s[4 * g + e], scale2, nl2));
+              dsum += pe * (DROP ? dp[4 * g + e] * mk[e] : dp[4 * g + e]);
+            }
+          } else if (allmasked) {
+            const f32x4 bias = *(const f32x4*)(tbias + cur * 64 + kl0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float pe = (bias[e] == FMIN && !(p.causal && (t * 64 + kl0 + e) > qidx)) ? uni_q : 0.f;
+              dsum += pe * (DROP ? dp[4 * g + e] * mk[e] : dp[4 * g + e]);
+            }
+          } else {
+            const f32x4 bias = *(const f32x4*)(tbias + cur * 64 + kl0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              float v = s[4 * g + e] * p.scale + bias[e];
+              if (p.causal && (t * 64 + kl0 + e) > qidx) v += FMIN;
+              const float pe = __expf(v - lse_q);                    // (exactly 0 for padding keys: bias = -inf)
+              dsum += pe * (DROP ? dp[4 * g + e] * mk[e] : dp[4 * g + e]);
+            }
+          }
+        }
+      }
+      if (t + 1 < ntile) put_bias(cur ^ 1, bn);        // (slot cur ^ 1 was last read before the previous tile's closing barrier)
+      lds_barrier();
+    }
+  }
+
+  // ---------------------------------------------------------------------------------------------- sweep 2: dK, dV, dQ
+  // The ring is idle behind sweep 1's last barrier: K of the first 128-key tile goes in while the delta partials meet.
+  const int ntile2 = (p.Tk + 127) >> 7;
+  char* ktile = ring;
+  char* vtile = ring + 2 * TILE_B;
+  float kbias = key_bias(wave * 32 + rl);
+  stage64(ks, ktile, 0, p.Tk, p.ldk, wave, lane);
+  stage64(ks, ktile + TILE_B, 64, p.Tk, p.ldk, wave, lane);
+  stage64(vs, vtile, 0, p.Tk, p.ldv, wave, lane);
+  stage64(vs, vtile + TILE_B, 64, p.Tk, p.ldv, wave, lane);
+  dsum += __shfl_xor(dsum, 32, 64);                    // the two lane halves hold different keys of the same query
+  if (hh == 0) part[wh * 64 + qidx] = dsum;            // (a wave without queries leaves 0)
+  lds_barrier();
+  if (wave == 0) {
+    const float d = part[lane] + part[64 + lane];      // (padding queries: every probability was 0)
+    stats[64 + lane] = d;
+    if (lane < p.Tq) p.delta_out[((long)b * p.H + hd) * p.Tq + lane] = d;
+  }
+
+  f32x16 dq = (f32x16)(0.f);
+  for (int t = 0; t < ntile2; ++t) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();                                     // K and V of tile t (and, the first time, delta) visible
+    // The LDS addresses of the fragment reads do not change from tile to tile, and hoisted out of this loop they take the
+    // registers the accumulators need (the kernel spilled): an opaque copy of the lane per phase keeps them, and everything
+    // else that is derived from the lane, inside.
+    int la = lane, lb = lane;
+    asm volatile("" : "+v"(la));
+    const int rl = la & 31, hh = la >> 5;
+    const int k0 = t * 128 + wave * 32, kidx = k0 + rl;
+    // every key of this wave unmasked and in range, no causal mask: the plain path
+    const bool plain = !p.causal && __builtin_amdgcn_ballot_w64(kbias != 0.f) == 0ull;
+    f32x16 dk[2], dv[2];
+    dk[0] = (f32x16)(0.f); dk[1] = (f32x16)(0.f); dv[0] = (f32x16)(0.f); dv[1] = (f32x16)(0.f);
+    {
+#pragma unroll
+      for (int qb2 = 0; qb2 < 2; ++qb2) {
+        if (qb2 < nqb) {
+          // this wave's K / V fragments (element j = K[k][16 s + 8 hh + j]; rows past Tk were zero-filled), read again for each
+          // query block: resident, they cost 32 registers the accumulators need
+          bf16x8 kf[4], vf[4];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) { kf[s] = frag_row(ktile, wave * 32, s, la); vf[s] = frag_row(vtile, wave * 32, s, la); }
+          f32x16 s = (f32x16)(0.f), dp = (f32x16)(0.f);
+#pragma unroll
+          for (int ks4 = 0; ks4 < 4; ++ks4) {
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(qt, qb2 * 32, ks4, la), kf[ks4], s, 0, 0, 0);
+            dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row(dot, qb2 * 32, ks4, la), vf[ks4], dp, 0, 0, 0);
+          }
+          uint32_t mb[4];
+          if (DROP) drop_block_queries(dctx, qb2 * 32 + 4 * hh, kidx, lane, mb);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int ql0 = qb2 * 32 + 8 * g + 4 * hh;
+            const f32x4 l4 = *(const f32x4*)(stats + ql0);
+            const f32x4 d4 = *(const f32x4*)(stats + 64 + ql0);
+            float mq[4] = {1.f, 1.f, 1.f, 1.f};
+            if (DROP) drop_word_factors(dctx, mb[g], mq);
+            // (dS carries no softmax scale here: dK and dQ are scaled once, on the way out)
+            if (plain) {
+              const f32x4 nl4 = *(const f32x4*)(stats + 128 + ql0);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float pe = __builtin_amdgcn_exp2f(fmaf(s[4 * g + e], scale2, nl4[e]));
+                s[4 * g + e] = DROP ? pe * mq[e] : pe;                                   // dV = (P o M)^T dO
+                dp[4 * g + e] = pe * ((DROP ? dp[4 * g + e] * mq[e] : dp[4 * g + e]) - d4[e]);    // dS = P o (dP o M - delta)
+              }
+            } else if (allmasked) {
+              const f32x4 u4 = *(const f32x4*)(stats + 192 + ql0);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                const float pe = (kbias == FMIN && !(p.causal && kidx > (ql0 + e))) ? u4[e] : 0.f;
+                s[4 * g + e] = DROP ? pe * mq[e] : pe;
+                dp[4 * g + e] = pe * ((DROP ? dp[4 * g + e] * mq[e] : dp[4 * g + e]) - d4[e]);
+              }
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                float v = s[4 * g + e] * p.scale + kbias;
+                if (p.causal && kidx > (ql0 + e)) v += FMIN;
+                const float pe = __expf(v - l4[e]);
+                s[4 * g + e] = DROP ? pe * mq[e] : pe;
+                dp[4 * g + e] = pe * ((DROP ? dp[4 * g + e] * mq[e] : dp[4 * g + e]) - d4[e]);
+              }
+            }
+            // dS^T[key][queries ql0 .. + 3], rounded as pack_acc rounds it for dK
+            const int row = wave * 32 + rl;
+            const u32x2 pk = {pack2bf(dp[4 * g], dp[4 * g + 1]), pack2bf(dp[4 * g + 2], dp[4 * g + 3])};
+            *(u32x2*)(dst + row * 128 + (((qb2 * 4 + g) ^ swz(row)) << 4) + 8 * hh) = pk;
+          }
+#pragma unroll
+          for (int ss = 0; ss < 2; ++ss) {
+            const bf16x8 pf = pack_acc(s, ss), dsf = pack_acc(dp, ss);
+#pragma unroll
+            for (int hb = 0; hb < 2; ++hb) {
+              dv[hb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(dot, qb2 * 32 + 16 * ss, hb * 32, la), pf, dv[hb], 0, 0, 0);
+              dk[hb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(qt, qb2 * 32 + 16 * ss, hb * 32, la), dsf, dk[hb], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+    lds_barrier();                                     // dS^T of the tile complete
+    if (t + 1 < ntile2) {                              // V of this tile is read by everyone: the next one goes in under the dQ step
+      kbias = key_bias(kidx + 128);
+      stage64(vs, vtile, (t + 1) * 128, p.Tk, p.ldv, wave, lane);
+      stage64(vs, vtile + TILE_B, (t + 1) * 128 + 64, p.Tk, p.ldv, wave, lane);
+    }
+    asm volatile("" : "+v"(lb));
+    if (qb < nqb) {
+#pragma unroll
+      for (int k16 = 0; k16 < 8; ++k16)
+        dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(ktile, 16 * k16, wh * 32, lb), frag_tr(dst, 16 * k16, qb * 32, lb), dq, 0, 0, 0);
+    }
+    lds_barrier();                                     // dS^T and the K tile read by everyone: dS^T is transposition space now
+    if (t + 1 < ntile2) {
+      stage64(ks, ktile, (t + 1) * 128, p.Tk, p.ldk, wave, lane);
+      stage64(ks, ktile + TILE_B, (t + 1) * 128 + 64, p.Tk, p.ldk, wave, lane);
+    }
+    if (p.rows16) {
+      if (k0 < p.Tk) {
+        char* ot = dst + wave * 4096;
+        store_rows32(ot, dk, p.scale, p.dk + (long)b * p.bsdk + (long)k0 * p.lddk + hd * 64, p.lddk, k0, p.Tk, lb);
+        store_rows32(ot, dv, 1.f, p.dv + (long)b * p.bsdv + (long)k0 * p.lddv + hd * 64, p.lddv, k0, p.Tk, lb);
+      }
+    } else if (kidx < p.Tk) {
+      bf16_t* dkrow = p.dk + (long)b * p.bsdk + (long)kidx * p.lddk + hd * 64;
+      bf16_t* dvrow = p.dv + (long)b * p.bsdv + (long)kidx * p.lddv + hd * 64;
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          u32x2 a = {pack2bf(dk[hb][4 * g] * p.scale, dk[hb][4 * g + 1] * p.scale), pack2bf(dk[hb][4 * g + 2] * p.scale, dk[hb][4 * g + 3] * p.scale)};
+          u32x2 c = {pack2bf(dv[hb][4 * g], dv[hb][4 * g + 1]), pack2bf(dv[hb][4 * g + 2], dv[hb][4 * g + 3])};
+          *(u32x2*)(dkrow + hb * 32 + 8 * g + 4 * hh) = a;
+          *(u32x2*)(dvrow + hb * 32 + 8 * g + 4 * hh) = c;
+        }
+    }
+  }
+
+  // dQ^T blocks -> [64 queries][128 B] in LDS (two waves fill each 32-row half), then whole rows
+  lds_barrier();                                       // the last tile's transposition reads are done
+  int le = lane;
+  asm volatile("" : "+v"(le));                         // (as in the loop: nothing derived from the lane lives across it)
+  if (qb < nqb) {
+    char* ot = dst + qb * 4096;
+    const int rl = le & 31, hh = le >> 5;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const u32x2 pk = {pack2bf(dq[4 * g] * p.scale, dq[4 * g + 1] * p.scale), pack2bf(dq[4 * g + 2] * p.scale, dq[4 * g + 3] * p.scale)};
+      *(u32x2*)(ot + rl * 128 + (((wh * 4 + g) ^ (rl & 7)) << 4) + 8 * hh) = pk;
+    }
+  }
+  lds_barrier();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = wave * 8 + (le >> 3), c16 = le & 7, row = i * 32 + r;
+    if (row < p.Tq) {
+      const u32x4 v = *(const u32x4*)(dst + i * 4096 + r * 128 + ((c16 ^ (r & 7)) << 4));
+      bf16_t* d = p.dq + (long)b * p.bsdq + (long)row * p.lddq + hd * 64 + c16 * 8;
+      if (p.rows16) *(u32x4*)d = v;
+      else { *(u32x2*)d = (u32x2){v[0], v[1]}; *(u32x2*)(d + 4) = (u32x2){v[2], v[3]}; }
+    }
   }
 }
 
@@ -895,6 +1260,7 @@ extern "C" int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream) {
   p.bsq = a->bsq; p.bsk = a->bsk; p.bsv = a->bsv; p.bso = a->bso;
   p.bsdq = a->bsdq; p.bsdk = a->bsdk; p.bsdv = a->bsdv;
   p.causal = a->causal; p.scale = a->scale;
+  p.rows16 = aligned16(a->dq) && aligned16(a->dk) && aligned16(a->dv);
   if (int e = set_dropout(p, a->p_drop, a->seed, a->seed_dev, "attn_bwd")) return e;
   hipStream_t s = (hipStream_t)stream;
   const long rows = (long)p.B * p.Tq;
@@ -902,6 +1268,20 @@ extern "C" int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream) {
   const dim3 gkv((unsigned)(((p.Tk + 127) / 128) * p.H * p.B)), gq((unsigned)(((p.Tq + 127) / 128) * p.H * p.B));
   const size_t lds_q = 4 * TILE_B + Tk_pad * 4 + (Tk_pad >> 6) * 4;
   p.delta_out = a->delta;
+  // Tq <= 64: one workgroup per (batch, head) does the whole backward, delta included
+  if (p.Tq <= 64) {
+    static bool once = false;                          // 66 KiB of dynamic LDS: both instantiations are told so once
+    if (!once) {
+      (void)hipFuncSetAttribute((const void*)attn_bwd_short_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SHORT_LDS);
+      (void)hipFuncSetAttribute((const void*)attn_bwd_short_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SHORT_LDS);
+      once = true;
+    }
+    const dim3 gbh((unsigned)(p.H * p.B));
+    if (p.drop_thr) hipLaunchKernelGGL(attn_bwd_short_kernel<true>, gbh, dim3(256), SHORT_LDS, s, p);
+    else hipLaunchKernelGGL(attn_bwd_short_kernel<false>, gbh, dim3(256), SHORT_LDS, s, p);
+    VLAUNCH_CHECK();
+    return VACNIC_OK;
+  }
   // delta: from the kernels' own P and dP (a sweep of the dQ kernel without its last product) for the decoder-sized problems,
   // where it costs microseconds; rowsum(dO o O) for the long encoder sequences
   if (p.Tq <= 128) {
