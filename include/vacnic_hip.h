@@ -362,8 +362,12 @@ int vacnic_name_embed_mean(const vacnic_name_embed_args* a, void* stream);
  * Also refreshes the bf16 shadow and zeroes the gradient.  grad_scale multiplies g first
  * (1/world_size for DDP averaging).  clip_coef (may be NULL): device pointer to the clip_grad_norm_
  * coefficient written by vacnic_grad_clip_coef; it multiplies g after grad_scale.
- * skip (may be NULL = never): device pointer to the verdict of vacnic_grad_guard (its state[0]).  When *skip != 0 the kernel
- * writes no p, m, v and no shadow (no weight decay either) and only zeroes g when zero_grad.
+ * skip (may be NULL = never): device pointer to the STEP WORD, an int64 that this entry point, vacnic_adamw_groups, vacnic_adamw_ema
+ * and vacnic_param_stats read and that vacnic_grad_guard (its state[0]) or vacnic_lr_step_accum (its accum[0]) writes:
+ *   0  apply the step
+ *   1  dropped by the guard: the kernel writes no p, m, v and no shadow (no weight decay either) and only zeroes g when zero_grad
+ *   2  hold (a micro-batch of an accumulation group that is not its last): the kernel returns before anything is read or written —
+ *      p, m, v, the shadow, ema AND g stay as they are, whatever zero_grad says
  */
 typedef struct {
   float* p; float* g; float* m; float* v; void* p_bf16; const float* hyper;
@@ -427,11 +431,14 @@ int vacnic_adamw_ema(const vacnic_adamw_ema_args* a, void* stream);
 int vacnic_ema_swap(float* p, float* ema, void* p_bf16, int64_t n, void* stream);
 /* vacnic_grad_clip_coef over the non-frozen elements only (clip_grad_norm_ sees no gradient for a parameter left out of the
  * optimizer): same fixed grid, per-thread order and reduction tree, so with no frozen segment the result is bitwise that of
- * vacnic_grad_clip_coef. */
+ * vacnic_grad_clip_coef.  Null table pointers: ungrouped, vacnic_grad_clip_coef itself (only elem_base counts).
+ * hold (may be NULL = never, as in a zero-initialised tail): device pointer to vacnic_lr_step_accum's accum.  When *hold == 2 both
+ * passes leave at once: the arena is not read and `out` keeps what it held. */
 typedef struct {
   const float* g; int64_t n; float grad_scale, max_norm; float* partials; float* out;
   const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
   int64_t nseg, nblocks, elem_base;
+  const int64_t* hold;
 } vacnic_grad_clip_groups_args;
 int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* a, void* stream);
 /*
@@ -452,12 +459,17 @@ int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* a, void* st
  *   hyper            on a skip hyper[1] -= 1, undoing vacnic_lr_step's increment: a dropped step advances neither Adam's t nor
  *                    the schedule position (the next vacnic_lr_step recomputes hyper[0] from the same k).  The dropout counter
  *                    that vacnic_lr_step advanced stays advanced: the retried position draws fresh masks.
+ *   hold             (may be NULL = never, as in a zero-initialised tail) device pointer to vacnic_lr_step_accum's accum.  When
+ *                    *hold == 2 pass 1 leaves at once without reading the arena and pass 2 writes state[0] = 2 and nothing else:
+ *                    nothing is counted, hyper and `out` stay.  On the group's last micro-batch (*hold == 0) the guard judges the
+ *                    accumulated gradient as above; a dropped group takes back the increment vacnic_lr_step_accum made.
  */
 typedef struct {
   const float* g; int64_t n; float grad_scale, max_norm; float* partials; int64_t* first_idx; float* out; int64_t* state;
   float* hyper;
   const int64_t* seg_start; const vacnic_adamw_seg* seg; const int32_t* first_seg;
   int64_t nseg, nblocks, elem_base;
+  const int64_t* hold;
 } vacnic_grad_guard_args;
 int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream);
 /*
@@ -485,9 +497,10 @@ int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream);
  *   pass 2  one workgroup per slot folds the slot's run of partials in unit order (a thread takes every 256th) through a fixed tree
  * Gate, evaluated by both passes from the same device values:
  *   hyper  float[2] (may be NULL), hyper[1] = the step count after vacnic_lr_step: the 1-based number of this step
- *   every  >= 1;   skip  (may be NULL) the guard's state
- *   the call FIRES when hyper == NULL, or (int64)hyper[1] % every == 0, or skip != NULL && *skip != 0 — a dropped step always records
- *   its statistics (its hyper[1] is the count after the guard took the increment back).
+ *   every  >= 1;   skip  (may be NULL) the step word (vacnic_adamw_args.skip): the guard's state or vacnic_lr_step_accum's accum
+ *   the call FIRES when hyper == NULL, or (int64)hyper[1] % every == 0, or skip != NULL && *skip == 1 — a dropped step always records
+ *   its statistics (its hyper[1] is the count after the guard took the increment back).  *skip == 2 (a held micro-batch of an
+ *   accumulation group) never fires, so `every` counts optimizer steps, as hyper[1] does.
  *   Not fired: nothing is written to out_f, out_i or stamp.
  *   Fired:     stamp int64[4] = {fires so far (incremented), (int64)hyper[1] as read (-1 if NULL), 1 if *skip != 0 else 0, 0};
  *              the caller zeroes stamp once.
@@ -508,6 +521,18 @@ int64_t vacnic_param_stats_workspace_bytes(int64_t nunit, int64_t nslot);
  * where k = hyper[1] on entry = optimizer steps already taken.  Also increments *rng_counter (the device-side
  * dropout counter, may be NULL).  Call once before vacnic_adamw. */
 int vacnic_lr_step(float* hyper, float base_lr, float warmup_steps, float total_steps, uint64_t* rng_counter, void* stream);
+/* vacnic_lr_step for gradient accumulation: k micro-batches per optimizer step, counted on the device, so that every micro-batch
+ * issues the same launches (backward accumulates into the fp32 gradient arena; the optimizer passes read the step word and act
+ * on the group's last micro-batch only).
+ *   accum  int64[4] = {step word, micro-batches pending, groups completed, 0}; the caller zeroes it once.
+ * Every call increments *rng_counter (each micro-batch draws fresh dropout masks).  Then
+ *   pending + 1 <  k:  pending += 1, step word = 2 (hold); hyper is untouched: neither the schedule position nor Adam's t moves
+ *   otherwise:         pending = 0, groups += 1, step word = 0 (apply); hyper advances exactly as in vacnic_lr_step
+ * Pass accum as `hold` to vacnic_grad_guard / vacnic_grad_clip_coef_groups, and as `skip` to vacnic_param_stats and vacnic_adamw*
+ * (with a guard: its state, which carries the hold on).  Callers scale the gradient by 1 / k (grad_scale): the mean of the k
+ * micro-batch gradients.  k == 1 is vacnic_lr_step bit for bit.  k < 1: status 1 before any launch. */
+int vacnic_lr_step_accum(float* hyper, float base_lr, float warmup_steps, float total_steps, uint64_t* rng_counter, int64_t* accum,
+                         int32_t k, void* stream);
 
 /* ---- small data-movement helpers on the path ------------------------------------------------- */
 /* f32 -> bf16 cast (weight shadow refresh, inputs). */

@@ -25,6 +25,7 @@ parser.set_defaults(only_image=True, no_mapping=True, use_secla=False, plm_type=
 run = _full.run
 build_config = _full.build_config
 train_args = _full.train_args
+accum_epoch_steps = _full.accum_epoch_steps
 
 
 if __name__ == "__main__":

@@ -105,6 +105,10 @@ parser.add_argument("--grad_stats_every", type=int, default=0, help="every N opt
                     "drops) record each parameter's gradient norm, largest gradient, weight norm, largest weight and its non-finite "
                     "and zero gradient elements, on the device; read at --log_every into the log record and, with --out_dir, into "
                     "<experiment_name>_gradstats.jsonl; 0 = off")
+# gradient accumulation of the optimizer (FusedAdamW(accum_steps=K)); 1 by default = every batch is an optimizer step
+parser.add_argument("--grad_accum_steps", type=int, default=1, help="K batches per optimizer step: the gradients of K batches are "
+                    "summed on the device and AdamW is applied to their mean, so one GPU reaches K times its batch size; the schedule "
+                    "counts optimizer steps, an epoch uses a multiple of K batches; one process only")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -127,8 +131,18 @@ def build_config(args):
     return cfg, ClipVisionConfig(**vkw)
 
 
+def accum_epoch_steps(steps_per_epoch, accum_steps):
+    """batches of an epoch that --grad_accum_steps K uses: the largest multiple of K, the remainder is left out like drop_last, so
+    that an epoch, and with it every checkpoint, ends on an optimizer step."""
+    used = (int(steps_per_epoch) // int(accum_steps)) * int(accum_steps)
+    if used <= 0:
+        raise ValueError(f"--grad_accum_steps {accum_steps}: an epoch of {steps_per_epoch} batches holds no whole optimizer step")
+    return used
+
+
 def train_args(args, total_steps):
-    """TrainArgs for the parsed flags."""
+    """TrainArgs for the parsed flags.  total_steps: batches of the whole run; with --grad_accum_steps K the schedule gets the
+    optimizer steps they make, total_steps // K."""
     from vacnic_amd.training import TrainArgs
     scales = []
     for item in args.lr_scale:
@@ -140,8 +154,11 @@ def train_args(args, total_steps):
         raise ValueError(f"--ema_decay {args.ema_decay!r}: expected a decay in (0, 1), or 0 for no average")
     if args.grad_stats_every < 0:
         raise ValueError(f"--grad_stats_every {args.grad_stats_every!r}: expected a number of steps >= 1, or 0 for none")
+    if args.grad_accum_steps < 1:
+        raise ValueError(f"--grad_accum_steps {args.grad_accum_steps!r}: expected a number of batches >= 1")
     return TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
-                     num_training_steps=total_steps, margin=args.margin, alpha=args.alpha,
+                     num_training_steps=total_steps // args.grad_accum_steps, grad_accum_steps=args.grad_accum_steps,
+                     margin=args.margin, alpha=args.alpha,
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
                      no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze),
@@ -190,11 +207,19 @@ def run(args, batches=None):
         steps_per_epoch = len(shard_loader)
         if steps_per_epoch <= 0:
             raise ValueError("the training shard holds fewer samples than one global batch")
-    total_steps = int(args.num_epoch) * steps_per_epoch          # TRAIN:99 (not divided by world size there either)
-    targs = train_args(args, total_steps)
+    accum = int(args.grad_accum_steps)
+    if accum > 1:
+        used = accum_epoch_steps(steps_per_epoch, accum)
+        if used != steps_per_epoch and rank == 0:
+            print(json.dumps({"grad_accum_steps": accum, "steps_per_epoch": steps_per_epoch, "used": used,
+                              "note": "the epoch's last batches make no whole optimizer step and are left out"}), flush=True)
+        steps_per_epoch = used
+    total_steps = int(args.num_epoch) * steps_per_epoch          # TRAIN:99 (not divided by world size there either); counted in batches
+    targs = train_args(args, total_steps)                        # (its num_training_steps: optimizer steps, total_steps // accum)
     net = DistributedDataParallel(model, device_ids=[local], output_device=local) if world > 1 else model
-    opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay, num_warmup_steps=args.warmup_rate * total_steps,
-                     num_training_steps=total_steps, world_size=world, param_groups=param_group_spec(model, targs),
+    opt = FusedAdamW(model.arena, lr=args.lr_bart, weight_decay=args.weight_decay,
+                     num_warmup_steps=args.warmup_rate * targs.num_training_steps, num_training_steps=targs.num_training_steps,
+                     accum_steps=accum, world_size=world, param_groups=param_group_spec(model, targs),
                      named_parameters=model.named_parameters(), skip_nonfinite=targs.skip_nonfinite,
                      ema_decay=targs.ema_decay or None, grad_stats_every=targs.grad_stats_every)
     stats_seen = 0                            # records of opt.grad_stats() already logged (rank 0)
@@ -240,6 +265,8 @@ def run(args, batches=None):
                                        seed=int(args.seed) % 65536, rank=rank, step=epoch * steps_per_epoch + i)
                   for i in range(steps_per_epoch))
         for bi, batch in enumerate(it):
+            if accum > 1 and bi >= steps_per_epoch:
+                break                                               # the remainder of the epoch: no whole optimizer step
             if epoch * steps_per_epoch + bi < start_step:
                 continue                                            # already consumed before the checkpoint
             if batches is None and step >= total_steps:
@@ -278,6 +305,8 @@ def run(args, batches=None):
                 tot, txt, secla, colam = out4.tolist()
                 rec = {"step": step, "loss": tot, "text loss": txt, "face name loss": secla, "margin loss": colam,
                        "samples_per_s": round((step - start_step) * args.train_batch_size * world / (time.time() - t0), 2)}
+                if accum > 1:
+                    rec["optimizer_step"] = opt.accum_report()["groups"]
                 if rep is not None:
                     rec["skipped"] = rep["skipped"]
                     rec["grad_norm"] = float(opt.clip[1].item())

@@ -172,11 +172,11 @@ AdamwEmaArgs = _struct("vacnic_adamw_ema_args", [
     ("ema", vp), ("ema_decay", f32), ("ema_warmup", i32)])
 
 GradClipGroupsArgs = _struct("vacnic_grad_clip_groups_args", [
-    ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("out", vp)] + _GROUP_TABLE)
+    ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("out", vp)] + _GROUP_TABLE + [("hold", vp)])
 
 GradGuardArgs = _struct("vacnic_grad_guard_args", [
     ("g", vp), ("n", i64), ("grad_scale", f32), ("max_norm", f32), ("partials", vp), ("first_idx", vp), ("out", vp), ("state", vp),
-    ("hyper", vp)] + _GROUP_TABLE)
+    ("hyper", vp)] + _GROUP_TABLE + [("hold", vp)])
 
 ParamStatsArgs = _struct("vacnic_param_stats_args", [
     ("g", vp), ("p", vp), ("n", i64), ("grad_scale", f32), ("unit_off", vp), ("unit_len", vp), ("nunit", i64),
@@ -201,6 +201,7 @@ _STRUCT_FNS = {
 _PLAIN_FNS = {
     "vacnic_combine_losses": [vp, vp, vp, vp, f32, f32, vp, vp],
     "vacnic_lr_step": [vp, f32, f32, f32, vp, vp],
+    "vacnic_lr_step_accum": [vp, f32, f32, f32, vp, vp, i32, vp],
     "vacnic_grad_clip_coef": [vp, i64, f32, f32, vp, vp, vp],
     "vacnic_ema_swap": [vp, vp, vp, i64, vp],
     "vacnic_cast_f32_bf16": [vp, vp, i64, vp],

@@ -12,10 +12,14 @@ embedding scatter sum through fp32 atomics whose order varies (VACNIC_WGRAD_GROU
              with FusedAdamW(skip_nonfinite=True) also "skipped": steps dropped so far (absent = 0; the run of consecutive drops
              restarts at 0).  "step" counts the steps APPLIED: it lags meta["step"], the trainer's data position, by "skipped";
              the two are restored separately.  With FusedAdamW(ema_decay=...) also "ema": {name: tensor}, the moving average of
-             the weights (load_checkpoint(..., weights="ema") loads it as the model's weights).
+             the weights (load_checkpoint(..., weights="ema") loads it as the model's weights).  With FusedAdamW(accum_steps=k > 1)
+             also "groups": groups of k batches completed so far (applied or dropped; absent = 0).
   schedule   {"base_lr", "num_warmup_steps", "num_training_steps", ...; "param_groups": the optimizer's parameter-group spec as plain
              data — present only when it has one; loading into an optimizer with another spec (or none) raises;
-             "ema_decay", "ema_warmup": present only with an average, informative (a resume may choose another decay)}
+             "ema_decay", "ema_warmup": present only with an average, informative (a resume may choose another decay);
+             "accum_steps": batches per optimizer step (absent = 1).  A checkpoint is written on a group boundary only (no
+             half-accumulated gradient is stored), and loads into an optimizer with the same accum_steps only: the schedule
+             is sized in optimizer steps and meta["step"], the data position, in batches}
   rng        {"seed", "counter", "device_counter"}      — Philox dropout seeds (ops.Rng); `seed` is rank-free, rank r uses seed + r
   meta       {"format": 1, "step": int, ...caller extras}
 Everything is moved to the CPU before `torch.save`, so a checkpoint loads on any box."""
@@ -70,6 +74,12 @@ def optimizer_state(model, optimizer):
         sd["ema"] = em
     if getattr(optimizer, "guard", None) is not None:
         sd["skipped"] = int(optimizer.guard[1].item())
+    if getattr(optimizer, "accum", None) is not None:
+        _, pending, groups, _ = optimizer.accum.tolist()       # (the device is idle: hyper was read above)
+        if pending != 0:
+            raise RuntimeError(f"save_checkpoint in the middle of an accumulation group: {pending} of {optimizer.accum_steps} batches "
+                               "are summed in the gradient arena, which a checkpoint does not store; save after the group's last batch")
+        sd["groups"] = int(groups)
     return sd
 
 
@@ -88,6 +98,8 @@ def save_checkpoint(path, model, optimizer=None, step=0, rank=0, **extra):
                                               for e in optimizer.param_groups]
         if getattr(optimizer, "ema_decay", None) is not None:
             ck["schedule"].update(ema_decay=optimizer.ema_decay, ema_warmup=optimizer.ema_warmup)
+        if getattr(optimizer, "accum_steps", 1) != 1:
+            ck["schedule"]["accum_steps"] = optimizer.accum_steps
     dev = ops.Rng.dev
     # `seed` is the run's seed WITHOUT the saving rank's offset (the trainer seeds rank r with seed + r): a resumed rank
     # re-derives its own base, so the data-parallel replicas keep drawing different dropout masks
@@ -139,6 +151,10 @@ def load_checkpoint(path_or_dict, model, optimizer=None, strict=True, rank=0, we
         saved, mine = ck.get("schedule", {}).get("param_groups"), getattr(optimizer, "param_groups", None)
         if saved != mine:
             raise ValueError(f"checkpoint was written with param_groups={saved!r}, the optimizer has param_groups={mine!r}")
+        saved, mine = int(ck.get("schedule", {}).get("accum_steps", 1)), getattr(optimizer, "accum_steps", 1)
+        if saved != mine:
+            raise ValueError(f"checkpoint was written with accum_steps={saved}, the optimizer has accum_steps={mine}: the schedule "
+                             "position counts optimizer steps of that many batches")
     with torch.no_grad():
         for name, p in targets:
             p.data.copy_(sd[name])
@@ -162,6 +178,9 @@ def load_checkpoint(path_or_dict, model, optimizer=None, strict=True, rank=0, we
         optimizer.hyper.copy_(torch.tensor([o["lr"], float(o["step"])]))
         if getattr(optimizer, "guard", None) is not None:
             optimizer.guard.copy_(torch.tensor([0, int(o.get("skipped", 0)), 0, -1], dtype=torch.int64))
+        if getattr(optimizer, "accum", None) is not None:
+            optimizer.accum.copy_(torch.tensor([0, 0, int(o.get("groups", 0)), 0], dtype=torch.int64))
+            a.grad.zero_()                               # a group begins: no batch of the run loaded over is pending any more
         r = ck.get("rng")
         if r is not None:
             seed = r["seed"] if "seed" in r else r["base"]          # "base": checkpoints written before the per-rank fix

@@ -8,15 +8,42 @@
 namespace {
 
 // hyper[0] = lr for this step, hyper[1] = step count t (float, 1-based after the increment)
+__device__ __forceinline__ void advance_schedule(float* hyper, float base_lr, float warmup, float total) {
+  const float k = hyper[1];                   // optimizer steps taken so far == LambdaLR's current_step
+  float lam;
+  if (k < warmup) lam = k / fmaxf(1.f, warmup);
+  else lam = fmaxf(0.f, (total - k) / fmaxf(1.f, total - warmup));
+  hyper[0] = base_lr * lam;
+  hyper[1] = k + 1.f;
+}
 __global__ void lr_step_kernel(float* hyper, float base_lr, float warmup, float total, unsigned long long* rng_counter) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     if (rng_counter) *rng_counter += 1ull;
-    const float k = hyper[1];                 // optimizer steps taken so far == LambdaLR's current_step
-    float lam;
-    if (k < warmup) lam = k / fmaxf(1.f, warmup);
-    else lam = fmaxf(0.f, (total - k) / fmaxf(1.f, total - warmup));
-    hyper[0] = base_lr * lam;
-    hyper[1] = k + 1.f;
+    advance_schedule(hyper, base_lr, warmup, total);
+  }
+}
+
+// ---- gradient accumulation: k micro-batches per optimizer step (vacnic_lr_step_accum, include/vacnic_hip.h) -------------------
+// The STEP WORD that AdamW, the statistics pass and the guard share: 0 apply, 1 dropped by the guard, 2 hold (a micro-batch that
+// only adds to the gradient).  Every micro-batch issues the launches of a full step; on a hold each of them loads the word and
+// leaves, so eager steps, launch plans and graphs need not know which kind of micro-batch they carry.
+constexpr int64_t kHold = 2;
+// accum = {step word, micro-batches pending, groups completed, 0}.  The dropout counter advances on every call (each micro-batch
+// draws its own masks); hyper only when the group is complete, with lr_step_kernel's arithmetic.
+__global__ void lr_step_accum_kernel(float* hyper, float base_lr, float warmup, float total, unsigned long long* rng_counter,
+                                     int64_t* accum, int k) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if (rng_counter) *rng_counter += 1ull;
+    const int64_t pending = accum[1];
+    if (pending + 1 < k) {
+      accum[1] = pending + 1;
+      accum[0] = kHold;
+    } else {
+      accum[1] = 0;
+      accum[2] += 1;
+      accum[0] = 0;
+      advance_schedule(hyper, base_lr, warmup, total);
+    }
   }
 }
 
@@ -31,7 +58,8 @@ __device__ __forceinline__ void skipped_step(float* __restrict__ g, long n4, int
 // clip_grad_norm_ (TRAIN:365-366), pass 2 (one workgroup) over the partial sums of grad_sumsq_kernel below:
 // out[0] = min(1, max_norm / (||g|| + 1e-6)), out[1] = ||g||
 __global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, int nparts, float max_norm,
-                                                             float* __restrict__ out) {
+                                                             float* __restrict__ out, const int64_t* __restrict__ hold) {
+  if (hold && *hold == kHold) return;           // a held micro-batch: pass 1 wrote no partial sums, out keeps the last group's pair
   float acc = 0.f;
   for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
   __shared__ float red[4];
@@ -97,7 +125,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
                                                     const float* __restrict__ hyper, long n4, float b1, float b2, float eps,
                                                     float wd, float gscale, int zero_grad, const float* __restrict__ clip,
                                                     GroupTable tab, const int64_t* __restrict__ skip, EmaArgs ea) {
-  if (skip && *skip) { skipped_step(g, n4, zero_grad); return; }      // grad_guard's verdict, one uniform branch: the average stays too
+  if (skip) {                                   // the step word, one uniform branch on one loaded value
+    const int64_t word = *skip;
+    if (word == kHold) return;                  // a held micro-batch: nothing is read or written, the gradient keeps accumulating
+    if (word) { skipped_step(g, n4, zero_grad); return; }             // grad_guard's verdict: the average stays too
+  }
   const float lr0 = hyper[0], t = hyper[1];
   if (clip) gscale *= clip[0];                  // clip_grad_norm_'s coefficient, computed on device by grad_clip_coef
   const float bc1 = 1.f - powf(b1, t), bc2 = 1.f - powf(b2, t);
@@ -191,7 +223,8 @@ __device__ __forceinline__ void guard_block_reduce(float& acc, long& first) {
 template <bool GROUPED, bool GUARD>
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n4, float gscale,
                                                          float* __restrict__ partials, int64_t* __restrict__ first_idx,
-                                                         GroupTable tab) {
+                                                         GroupTable tab, const int64_t* __restrict__ hold) {
+  if (hold && *hold == kHold) return;           // a held micro-batch: the arena is not read (uniform: the whole grid leaves)
   float acc = 0.f;
   long first = INT64_MAX;
   auto add = [&](float ge, long a) {                      // a rises within a thread: its first hit is its smallest
@@ -240,7 +273,11 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void grad_guard_verdict_kernel(const float* __restrict__ partials,
                                                                  const int64_t* __restrict__ first_idx, int nparts, float max_norm,
                                                                  float* __restrict__ out, int64_t* __restrict__ state,
-                                                                 float* __restrict__ hyper) {
+                                                                 float* __restrict__ hyper, const int64_t* __restrict__ hold) {
+  if (hold && *hold == kHold) {                 // a held micro-batch: the verdict is "hold", nothing is counted, out and hyper stay
+    if (threadIdx.x == 0) state[0] = kHold;
+    return;
+  }
   float acc = 0.f;
   long first = INT64_MAX;
   for (int i = threadIdx.x; i < nparts; i += 256) {
@@ -338,10 +375,11 @@ int adamw_launch(const AdamwCall& c, void* stream) {
 
 // pass 1 of the norm: a table picks GROUPED (without one only tab.elem_base counts), first_idx picks GUARD
 void launch_grad_sumsq(const float* g, int64_t n, float gscale, float* partials, int64_t* first_idx, const GroupTable& tab,
-                       void* stream) {
+                       const int64_t* hold, void* stream) {
   const auto kernel = has_table(tab) ? (first_idx ? grad_sumsq_kernel<true, true> : grad_sumsq_kernel<true, false>)
                                      : (first_idx ? grad_sumsq_kernel<false, true> : grad_sumsq_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, g, (long)(n >> 2), gscale, partials, first_idx, tab);
+  hipLaunchKernelGGL(kernel, dim3(kNormBlocks), dim3(256), 0, (hipStream_t)stream, g, (long)(n >> 2), gscale, partials, first_idx, tab,
+                     hold);
 }
 
 }  // namespace
@@ -350,6 +388,18 @@ extern "C" int vacnic_lr_step(float* hyper, float base_lr, float warmup_steps, f
   VPLAN_REC(vacnic_lr_step, hyper, base_lr, warmup_steps, total_steps, rng_counter, stream);
   VCHECK(hyper, VACNIC_BAD_SHAPE, "lr_step: null hyper");
   hipLaunchKernelGGL(lr_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, base_lr, warmup_steps, total_steps, (unsigned long long*)rng_counter);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_lr_step_accum(float* hyper, float base_lr, float warmup_steps, float total_steps, uint64_t* rng_counter,
+                                    int64_t* accum, int32_t k, void* stream) {
+  VPLAN_REC(vacnic_lr_step_accum, hyper, base_lr, warmup_steps, total_steps, rng_counter, accum, k, stream);
+  VCHECK(hyper && accum, VACNIC_BAD_SHAPE, "lr_step_accum: null operand");
+  VCHECK(k >= 1, VACNIC_BAD_SHAPE, "lr_step_accum: k=%d micro-batches per optimizer step must be >= 1", (int)k);
+  VCHECK(((uintptr_t)accum & 7) == 0, VACNIC_MISALIGNED, "lr_step_accum: accum must be 8-byte aligned");
+  hipLaunchKernelGGL(lr_step_accum_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, base_lr, warmup_steps, total_steps,
+                     (unsigned long long*)rng_counter, accum, (int)k);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
@@ -367,9 +417,10 @@ extern "C" int vacnic_grad_clip_coef(const float* g, int64_t n, float grad_scale
   VCHECK(g && partials && out, VACNIC_BAD_SHAPE, "grad_clip_coef: null operand");
   VCHECK((n & 3) == 0 && aligned16(g), VACNIC_BAD_SHAPE, "grad_clip_coef: arena must be 16-byte aligned, n=%ld a multiple of 4", (long)n);
   VCHECK(max_norm > 0.f, VACNIC_BAD_SHAPE, "grad_clip_coef: max_norm must be > 0");
-  launch_grad_sumsq(g, n, grad_scale, partials, nullptr, GroupTable{}, stream);
+  launch_grad_sumsq(g, n, grad_scale, partials, nullptr, GroupTable{}, nullptr, stream);
   VLAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, kNormBlocks, max_norm, out);
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, kNormBlocks, max_norm, out,
+                     (const int64_t*)nullptr);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
@@ -409,11 +460,16 @@ extern "C" int vacnic_grad_clip_coef_groups(const vacnic_grad_clip_groups_args* 
   VCHECK(a->n >= 0 && (a->n & 3) == 0 && aligned16(a->g), VACNIC_BAD_SHAPE,
          "grad_clip_coef_groups: arena must be 16-byte aligned, n=%ld a multiple of 4", (long)a->n);
   VCHECK(a->max_norm > 0.f, VACNIC_BAD_SHAPE, "grad_clip_coef_groups: max_norm must be > 0");
+  VCHECK(a->elem_base >= 0, VACNIC_BAD_SHAPE, "grad_clip_coef_groups: elem_base=%ld must be >= 0", (long)a->elem_base);
+  VCHECK(((uintptr_t)a->hold & 7) == 0, VACNIC_MISALIGNED, "grad_clip_coef_groups: hold must be 8-byte aligned");
   const GroupTable tab = table_of(a);
-  if (const int err = check_group_table(tab, a->n, "grad_clip_coef_groups")) return err;
-  launch_grad_sumsq(a->g, a->n, a->grad_scale, a->partials, nullptr, tab, stream);
+  if (has_table(tab)) {                          // null table pointers: ungrouped, as vacnic_grad_guard reads them
+    if (const int err = check_group_table(tab, a->n, "grad_clip_coef_groups")) return err;
+  }
+  launch_grad_sumsq(a->g, a->n, a->grad_scale, a->partials, nullptr, tab, a->hold, stream);
   VLAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, kNormBlocks, a->max_norm, a->out);
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, kNormBlocks, a->max_norm, a->out,
+                     a->hold);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }
@@ -424,15 +480,16 @@ extern "C" int vacnic_grad_guard(const vacnic_grad_guard_args* a, void* stream) 
   VCHECK(a->n >= 0 && (a->n & 3) == 0 && aligned16(a->g), VACNIC_BAD_SHAPE,
          "grad_guard: arena must be 16-byte aligned, n=%ld a multiple of 4", (long)a->n);
   VCHECK(a->elem_base >= 0, VACNIC_BAD_SHAPE, "grad_guard: elem_base=%ld must be >= 0", (long)a->elem_base);
-  VCHECK(((uintptr_t)a->first_idx & 7) == 0 && ((uintptr_t)a->state & 7) == 0, VACNIC_MISALIGNED, "grad_guard: first_idx and state must be 8-byte aligned");
+  VCHECK(((uintptr_t)a->first_idx & 7) == 0 && ((uintptr_t)a->state & 7) == 0 && ((uintptr_t)a->hold & 7) == 0, VACNIC_MISALIGNED,
+         "grad_guard: first_idx, state and hold must be 8-byte aligned");
   const GroupTable tab = table_of(a);
   if (has_table(tab)) {
     if (const int err = check_group_table(tab, a->n, "grad_guard")) return err;
   }
-  launch_grad_sumsq(a->g, a->n, a->grad_scale, a->partials, a->first_idx, tab, stream);
+  launch_grad_sumsq(a->g, a->n, a->grad_scale, a->partials, a->first_idx, tab, a->hold, stream);
   VLAUNCH_CHECK();
   hipLaunchKernelGGL(grad_guard_verdict_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a->partials, a->first_idx, kNormBlocks,
-                     a->max_norm, a->out, a->state, a->hyper);
+                     a->max_norm, a->out, a->state, a->hyper, a->hold);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

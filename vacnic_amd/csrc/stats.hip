@@ -18,8 +18,10 @@ struct Gate { long t; int on_skip; bool fire; };
 __device__ __forceinline__ Gate read_gate(const float* __restrict__ hyper, int every, const int64_t* __restrict__ skip) {
   Gate g;
   g.t = hyper ? (long)hyper[1] : -1;
-  g.on_skip = (skip && *skip != 0) ? 1 : 0;
-  g.fire = !hyper || g.on_skip || (g.t % every) == 0;
+  const int64_t word = skip ? *skip : 0;        // the step word (optim.hip): 0 apply, 1 dropped by the guard, 2 hold
+  g.on_skip = word != 0 ? 1 : 0;
+  // a held micro-batch of an accumulation group never fires: the gradient is a partial sum, and hyper[1] has not moved
+  g.fire = word != 2 && (!hyper || g.on_skip || (g.t % every) == 0);
   return g;
 }
 

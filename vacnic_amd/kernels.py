@@ -568,6 +568,19 @@ def lr_step(hyper, base_lr, warmup, total, rng_counter=None):
     call("vacnic_lr_step", hyper.data_ptr(), base_lr, float(warmup), float(total), _p(rng_counter), _stream())
 
 
+def accum_state(device):
+    """the int64[4] state of lr_step_accum(): {step word, micro-batches pending, groups completed, 0}."""
+    return torch.zeros(4, device=device, dtype=torch.int64)
+
+
+def lr_step_accum(hyper, base_lr, warmup, total, accum, k, rng_counter=None):
+    """lr_step() for k micro-batches per optimizer step, counted on the device: every call advances the dropout counter; the first
+    k - 1 calls of a group set accum[0] = 2 (hold) and leave hyper alone, the k-th sets it to 0 and advances hyper as lr_step does.
+    Pass accum as `hold` to grad_guard / grad_clip_coef_groups and as `skip` to param_stats / adamw* (with a guard: its state)."""
+    assert accum.dtype == torch.int64 and accum.numel() >= 4
+    call("vacnic_lr_step_accum", hyper.data_ptr(), base_lr, float(warmup), float(total), _p(rng_counter), _p(accum), int(k), _stream())
+
+
 def _adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip):
     """the struct fields that vacnic_adamw, vacnic_adamw_groups and vacnic_adamw_ema have in common."""
     return dict(p=_p(p), g=_p(g), m=_p(m), v=_p(v), p_bf16=_p(p16), hyper=_p(hyper), n=n, beta1=beta1, beta2=beta2, eps=eps,
@@ -595,7 +608,8 @@ def _norm_scratch(g, partials, out):
 
 def adamw(p, g, m, v, p16, hyper, n, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, grad_scale=1.0, zero_grad=True,
           clip_coef=None, skip=None):
-    """skip: the int64 state of grad_guard() (or None): when its flag is set the step only zeroes g."""
+    """skip: the int64 state of grad_guard() or of lr_step_accum() (or None): when its word is 1 the step only zeroes g, when it is 2
+    (a held micro-batch) the step does nothing at all."""
     call_struct("vacnic_adamw", stream=_stream(), weight_decay=weight_decay,
                 **_adamw_fields(p, g, m, v, p16, hyper, n, beta1, beta2, eps, grad_scale, zero_grad, clip_coef, skip))
 
@@ -632,11 +646,12 @@ def ema_swap(p, ema, p16=None):
     call("vacnic_ema_swap", _p(p), _p(ema), _p(p16), p.numel(), _stream())
 
 
-def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0):
-    """grad_clip_coef() over the non-frozen segments of the table."""
+def grad_clip_coef_groups(g, n, max_norm, table, grad_scale=1.0, partials=None, out=None, elem_base=0, hold=None):
+    """grad_clip_coef() over the non-frozen segments of the table (None: ungrouped).  hold: the state of lr_step_accum() or None;
+    on a held micro-batch the arena is not read and `out` stays."""
     partials, out = _norm_scratch(g, partials, out)
     call_struct("vacnic_grad_clip_coef_groups", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=max_norm,
-                partials=_p(partials), out=_p(out), **_group_table(table, elem_base))
+                partials=_p(partials), out=_p(out), hold=_p(hold), **_group_table(table, elem_base))
     return out
 
 
@@ -646,10 +661,11 @@ def guard_state(device):
 
 
 def grad_guard(g, n, hyper, state=None, max_norm=0.0, table=None, grad_scale=1.0, partials=None, first_idx=None, out=None,
-               elem_base=0):
+               elem_base=0, hold=None):
     """Non-finite gradient guard on device (no sync): call between lr_step() and adamw(skip=state).  Writes out = {clip coefficient,
     norm} as grad_clip_coef[_groups] does (max_norm <= 0: coefficient 1), the verdict and counters into `state`, and on a skip takes
     lr_step's increment of hyper[1] back.  table: a parameter-group table (frozen segments are left out) or None.
+    hold: the state of lr_step_accum() or None; on a held micro-batch the guard only writes state[0] = 2.
     Returns (out, state)."""
     if state is None:
         state = guard_state(g.device)
@@ -659,7 +675,7 @@ def grad_guard(g, n, hyper, state=None, max_norm=0.0, table=None, grad_scale=1.0
     assert first_idx.dtype == torch.int64 and first_idx.numel() >= 1024 and state.dtype == torch.int64 and state.numel() >= 4
     call_struct("vacnic_grad_guard", stream=_stream(), g=_p(g), n=n, grad_scale=grad_scale, max_norm=float(max_norm),
                 partials=_p(partials), first_idx=_p(first_idx), out=_p(out), state=_p(state), hyper=_p(hyper),
-                **_group_table(table, elem_base))
+                hold=_p(hold), **_group_table(table, elem_base))
     return out, state
 
 
@@ -671,7 +687,8 @@ def param_stats_workspace(table, device):
 
 def param_stats(g, p, n, table, hyper=None, every=1, skip=None, grad_scale=1.0, workspace=None, out_f=None, out_i=None, stamp=None):
     """Per-slot statistics of the gradient arena g (and the weights p, or None) on device, gated on device (no sync): fires when
-    hyper is None, when int(hyper[1]) % every == 0, or when skip (grad_guard's state) is set; otherwise nothing is written.
+    hyper is None, when int(hyper[1]) % every == 0, or when skip (grad_guard's state) is 1; otherwise, and always on a held
+    micro-batch (skip's word is 2: grad_guard's or lr_step_accum's state), nothing is written.
     table: arena.stats_table(...).to(device).  out_f float[nslot][4] = {sum x^2, max |x| over finite x = g * grad_scale, sum p^2,
     max |p|}, out_i int64[nslot][2] = {non-finite elements, elements with g == 0}, stamp int64[4] = {fires so far, hyper[1] as
     read, fired on a skip, 0}; allocated (zeroed) where not given.  Returns (out_f, out_i, stamp)."""

@@ -39,6 +39,7 @@ class TrainArgs:
     skip_nonfinite: bool = False          # --skip_nonfinite: drop a step whose reduced gradient is not finite (FusedAdamW)
     ema_decay: float = 0.0                # --ema_decay: moving average of the weights inside the AdamW step (FusedAdamW); 0 = off
     grad_stats_every: int = 0             # --grad_stats_every N: per-parameter gradient / weight statistics every N steps (FusedAdamW)
+    grad_accum_steps: int = 1             # --grad_accum_steps K: K batches per optimizer step (FusedAdamW(accum_steps=K)); one process
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -59,8 +60,15 @@ class FusedAdamW:
 
     def __init__(self, arena, lr, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, num_warmup_steps=0.0,
                  num_training_steps=1.0, world_size=1, param_groups=None, named_parameters=None, skip_nonfinite=False,
-                 ema_decay=None, ema_warmup=True, grad_stats_every=None):
-        """grad_stats_every: N >= 1 records per-parameter statistics of the averaged gradient and of the weights (K.param_stats:
+                 ema_decay=None, ema_warmup=True, grad_stats_every=None, accum_steps=1):
+        """accum_steps: k > 1 makes k calls of step() one optimizer step over the mean of k batch gradients (gradient accumulation).
+        Backward accumulates into the fp32 gradient arena already; every step() issues the launches of a full step, and a counter on
+        the device (K.lr_step_accum) lets the first k - 1 of a group leave at once: weights, moments, the shadow, the average, the
+        schedule position and Adam's t stay, the gradient is kept.  The k-th applies AdamW to the sum scaled by 1 / k and zeroes it.
+        Eager steps, launch plans and graphs therefore run unchanged, whichever micro-batch they were recorded on.  The guard, the
+        clip norm and the statistics see the group's mean gradient, once per group; the dropout counter advances per batch.
+        accum_report() reads the counters.  One process only (world_size == 1).  1 (default): the launches of before.
+        grad_stats_every: N >= 1 records per-parameter statistics of the averaged gradient and of the weights (K.param_stats:
         norm and largest magnitude of both, non-finite and exactly-zero gradient elements) on every step whose 1-based count is a
         multiple of N, and on every step the guard drops; decided on the device, so eager steps, launch plans and graphs run the
         same launches.  grad_stats() reads the most recent record.  They do not depend on parameter groups (a frozen parameter's
@@ -83,6 +91,12 @@ class FusedAdamW:
             raise ValueError(f"FusedAdamW: ema_decay={ema_decay!r} must lie in (0, 1) (None: no average)")
         if grad_stats_every is not None and int(grad_stats_every) < 0:
             raise ValueError(f"FusedAdamW: grad_stats_every={grad_stats_every!r} must be >= 0 (0 or None: off)")
+        if int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise ValueError(f"FusedAdamW: accum_steps={accum_steps!r} must be an integer >= 1 (1: every batch is an optimizer step)")
+        if int(accum_steps) > 1 and world_size > 1:
+            raise ValueError(f"FusedAdamW: accum_steps={accum_steps} with world_size={world_size}: the reducer all-reduces the gradient "
+                             "arena in place, so a second micro-batch's reduction would multiply the already reduced sums by the "
+                             "world size; accumulation runs in one process")
         self.arena = arena
         arena.init_optimizer_state()
         self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
@@ -111,6 +125,11 @@ class FusedAdamW:
             self.clip = torch.zeros(2, device=arena.device, dtype=torch.float32)
             self._clip_scratch = torch.empty(1024, device=arena.device, dtype=torch.float32)
             self._guard_scratch = torch.empty(1024, device=arena.device, dtype=torch.int64)
+        self.accum_steps = int(accum_steps)
+        self.accum = None                 # int64 {step word, micro-batches pending, groups completed, 0} (K.lr_step_accum)
+        if self.accum_steps > 1:
+            # allocated here, not in the first step: a launch plan replays the recorded addresses
+            self.accum = K.accum_state(arena.device)
         self.grad_stats_every = int(grad_stats_every or 0)
         self._stats = None                # (table, workspace, out_f, out_i, stamp) of K.param_stats
         if self.grad_stats_every:
@@ -128,34 +147,47 @@ class FusedAdamW:
         coefficient stays in device memory and is applied where the AdamW kernel reads the gradient."""
         a = self.arena
         self._not_swapped("step()")
-        K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())   # also advances the dropout counter
+        scale = self._grad_scale()
+        if self.accum is None:
+            K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())   # also advances the dropout counter
+        else:
+            # the same launches on every micro-batch; on the first k - 1 of a group each of them reads the step word and leaves
+            K.lr_step_accum(self.hyper, self.lr, self.warmup, self.total, self.accum, self.accum_steps, ops.Rng.device_counter())
         clip = None
         if self.skip_nonfinite:
             # the guard's norm pass is the clip's: one pass gives the verdict and {coefficient, norm}
             K.grad_guard(a.grad, a.n, self.hyper, self.guard, 0.0 if clip_norm is None else float(clip_norm), self.table,
-                         1.0 / self.world, self._clip_scratch, self._guard_scratch, self.clip)
+                         scale, self._clip_scratch, self._guard_scratch, self.clip, hold=self.accum)
             clip = None if clip_norm is None else self.clip
         elif clip_norm is not None:
             if self.clip is None:
                 self.clip = torch.zeros(2, device=a.device, dtype=torch.float32)
                 self._clip_scratch = torch.empty(1024, device=a.device, dtype=torch.float32)
-            if self.table is None:
-                clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), 1.0 / self.world, self._clip_scratch, self.clip)
+            if self.accum is not None:         # (the entry point that takes `hold`; without a table it is the ungrouped pass)
+                clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, scale, self._clip_scratch, self.clip,
+                                               hold=self.accum)
+            elif self.table is None:
+                clip = K.grad_clip_coef(a.grad, a.n, float(clip_norm), scale, self._clip_scratch, self.clip)
             else:
-                clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, 1.0 / self.world, self._clip_scratch, self.clip)
+                clip = K.grad_clip_coef_groups(a.grad, a.n, float(clip_norm), self.table, scale, self._clip_scratch, self.clip)
+        # the step word AdamW and the statistics read: the guard's verdict (which carries a hold on), else the accumulation counter's
+        word = self.guard if self.guard is not None else self.accum
         if self._stats is not None:
             # after the guard (its verdict fires the record of a dropped step), before the update zeroes the gradient
             tab, work, out_f, out_i, stamp = self._stats
-            K.param_stats(a.grad, a.flat32, a.n, tab, self.hyper, self.grad_stats_every, self.guard, 1.0 / self.world, work,
-                          out_f, out_i, stamp)
-        self._update(0, a.n, clip, self.guard)
+            K.param_stats(a.grad, a.flat32, a.n, tab, self.hyper, self.grad_stats_every, word, scale, work, out_f, out_i, stamp)
+        self._update(0, a.n, clip, word)
+
+    def _grad_scale(self):
+        """what turns the arena's sum into the mean gradient: over the ranks, and over the micro-batches of a group"""
+        return 1.0 / (self.world * self.accum_steps)
 
     def _update(self, start, end, clip, skip):
         """the AdamW launch over arena elements [start, end): the one place that chooses among the three entry points."""
         a = self.arena
         r = slice(start, end)
         bufs = (a.flat32[r], a.grad[r], a.exp_avg[r], a.exp_avg_sq[r], a.flat16[r], self.hyper, end - start)
-        kw = dict(beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, grad_scale=1.0 / self.world, zero_grad=True,
+        kw = dict(beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, grad_scale=self._grad_scale(), zero_grad=True,
                   clip_coef=clip, skip=skip)
         if self.ema_decay is not None:
             K.adamw_ema(*bufs, a.ema[r], self.ema_decay, self.ema_warmup, self.table, start, weight_decay=self.wd, **kw)
@@ -177,6 +209,14 @@ class FusedAdamW:
             from .arena import name_at
             name = name_at(self.arena, named_parameters, first)
         return {"skipped": skipped, "in_a_row": run, "first_nonfinite": name, "offset": first}
+
+    def accum_report(self):
+        """The one method of gradient accumulation that synchronises (a 32-byte read): {"accum_steps": k, "pending": micro-batches
+        added to the gradient since the last optimizer step, "groups": groups of k completed so far, dropped ones included}."""
+        if self.accum is None:
+            raise RuntimeError("accum_report(): the optimizer was built with accum_steps=1")
+        _, pending, groups, _ = (int(x) for x in self.accum.tolist())
+        return {"accum_steps": self.accum_steps, "pending": pending, "groups": groups}
 
     def grad_stats(self, named_parameters):
         """The one method of the statistics that synchronises: the most recent record as
@@ -210,6 +250,8 @@ class FusedAdamW:
             raise RuntimeError("skip_nonfinite needs the whole reduced gradient before any range is updated: use step()")
         if self.grad_stats_every:
             raise RuntimeError("grad_stats_every needs the whole reduced gradient before any range is zeroed: use step()")
+        if self.accum_steps > 1:
+            raise RuntimeError("accum_steps > 1 holds the whole update back until the group's last batch: use step()")
         self._not_swapped("begin_step()")
         K.lr_step(self.hyper, self.lr, self.warmup, self.total, ops.Rng.device_counter())
 
@@ -218,7 +260,7 @@ class FusedAdamW:
         self._update(start, end, None, None)
 
     def zero_grad(self):
-        pass            # fused into step(): the AdamW kernel clears the gradient arena it just consumed
+        pass            # fused into step(): the AdamW kernel clears the gradient arena it just consumed (and keeps it on a held micro-batch)
 
     # ---- moving average of the weights ------------------------------------------------------------------------------------
     def _not_swapped(self, what):
@@ -460,6 +502,12 @@ def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towe
     stats = getattr(optimizer, "grad_stats_every", 0)
     if args.grad_stats_every and not stats:
         raise ValueError("TrainArgs.grad_stats_every needs an optimizer built with FusedAdamW(..., grad_stats_every=N)")
+    accum = getattr(optimizer, "accum_steps", 1)
+    if args.grad_accum_steps != accum:
+        raise ValueError(f"TrainArgs.grad_accum_steps={args.grad_accum_steps} but the optimizer was built with accum_steps={accum}")
+    if accum > 1 and isinstance(model, DistributedDataParallel) and model.active:
+        raise ValueError("grad_accum_steps > 1 under an active DistributedDataParallel: the reducer all-reduces the gradient arena in "
+                         "place, which would multiply the already reduced micro-batch sums by the world size")
     pipelined = (isinstance(model, DistributedDataParallel) and model.native is not None and model.active and clip is None
                  and not guarded and not stats)
     streams.join_all(skip_wgrad=pipelined)   # side streams -> compute stream
