@@ -724,6 +724,36 @@ int vacnic_lmhead_ce_rowp_smooth(const float* row_lse, const int64_t* targets, c
 int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t col0, int64_t ncols, void* dl, int64_t lddl,
                              const float* rowp, void* stream);
 
+/*
+ * Fused validation head: teacher-forced token log-probabilities, greedy predictions and per-caption sums from ONE LM-head pass,
+ * again WITHOUT the [R, V] logits.  The forward GEMM of vacnic_lmhead_ce_fwd runs with a third epilogue (a kernel of its own; the
+ * kernels vacnic_lmhead_ce_fwd launches are untouched): besides part[R][part_tiles][2] = {max, sum exp} and tl[R] it writes
+ * part_arg[R][part_tiles], the GLOBAL column of each tile's largest logit among the valid columns n < V (after the bias; ties go
+ * to the lowest column; the zero rows that pad the embedding beyond V never take part).  A combine kernel (one wave per row) writes
+ *   row_lse[r]   bit-identical to vacnic_lmhead_ce_fwd's on the same operands,
+ *   row_nll[r] = row_lse[r] - logit[r][target[r]], an exact 0 where target[r] == ignore_index,
+ *   pred[r]      argmax_j logit[r][j] over j < V (larger value, then lower index), for ignored rows too;
+ * a per-caption kernel sums each run of rows_per_seq consecutive rows in a fixed order:
+ *   seq_nll[s] (f32), seq_tokens[s] = rows with target != ignore_index, seq_correct[s] = those of them with pred == target;
+ * and, when totals != NULL, one workgroup adds this call's sums in index order onto the running record
+ *   totals[4] (f64) += {sum seq_nll, sum seq_tokens, sum seq_correct, R / rows_per_seq}.
+ * The caller zeroes totals once per validation pass with vacnic_zero_bytes; the call itself issues no memset (see
+ * vacnic_zero_bytes: a memset node is unsafe under capture) and no floating-point atomic, so every output is bit-reproducible.
+ * Scratch: part R * part_tiles * 2 floats, part_arg R * part_tiles int32, tl R floats; all contiguous, 4-byte stores.
+ * Domain of the targets: as for vacnic_lmhead_ce_fwd, in [0, V) or equal to ignore_index.
+ * VACNIC_BAD_SHAPE before any launch: a null operand (bias and totals may be NULL), R % rows_per_seq != 0,
+ * part_tiles != ceil(V / 256).
+ */
+typedef struct {
+  const void* h; const void* emb; const float* bias; const int64_t* targets;
+  float* part; int32_t* part_arg; float* tl;                 /* scratch: [R][part_tiles][2], [R][part_tiles], [R] */
+  float* row_lse; float* row_nll; int64_t* pred;             /* [R] */
+  float* seq_nll; int32_t* seq_tokens; int32_t* seq_correct; /* [R / rows_per_seq] */
+  double* totals;                                            /* [4], accumulated; may be NULL */
+  int64_t R, V, D, ldh, lde, part_tiles, ignore_index, rows_per_seq;
+} vacnic_lmhead_eval_args;
+int vacnic_lmhead_eval(const vacnic_lmhead_eval_args* a, void* stream);
+
 /* zero `bytes` bytes at `ptr` on `stream`: the fp32 accumulators of split-K GEMMs, the arrival counters of the split-K fix-up.
  * hipMemsetAsync on an ordinary stream; a fill kernel while `stream` is being captured into a hipGraph (a memset NODE is not
  * reliably ordered before the kernel node that follows it when the graph replays). */

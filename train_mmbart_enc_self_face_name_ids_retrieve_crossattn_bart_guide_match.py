@@ -109,6 +109,9 @@ parser.add_argument("--grad_stats_every", type=int, default=0, help="every N opt
 parser.add_argument("--grad_accum_steps", type=int, default=1, help="K batches per optimizer step: the gradients of K batches are "
                     "summed on the device and AdamW is applied to their mean, so one GPU reaches K times its batch size; the schedule "
                     "counts optimizer steps, an epoch uses a multiple of K batches; one process only")
+# fused validation head (vacnic_amd.training.eval_epoch_fused); off by default = eval_epoch, as in the reference
+parser.add_argument("--eval_fused", default=False, type=_b, help="validate with one LM-head pass per batch that never writes the "
+                    "logits and waits for the device once per pass; the epoch record gains the token accuracy and the perplexity")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -175,8 +178,8 @@ def run(args, batches=None):
     import torch.distributed as dist
     from vacnic_amd import ops, streams, synthetic
     from vacnic_amd.ddp import DistributedDataParallel
-    from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, build_models, eval_epoch, gen_caption_from_loader_bart, param_group_spec,
-                                     to_device, train_step)
+    from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, build_models, eval_epoch, eval_epoch_fused, gen_caption_from_loader_bart,
+                                     param_group_spec, to_device, train_step)
 
     if not args.no_clip_loss or not args.freeze_clip:
         raise NotImplementedError("CLIP contrastive loss / CLIP fine-tuning are out of scope (SURVEY §2 row 20): pass --no_clip_loss True --freeze_clip True")
@@ -331,9 +334,15 @@ def run(args, batches=None):
             # TRAIN:455-470: validation pass per epoch; the best model and its teacher-forced outputs are kept
             vb = (synthetic.make_batch(cfg, args.val_batch_size, S=args.article_max_length, T=min(64, args.caption_max_length),
                                        seed=(int(args.seed) + 7919) % 65536, rank=0, step=i) for i in range(args.val_steps))
+            vrec = {"epoch": epoch}
             with eval_weights():
-                val_loss, vdict = eval_epoch(net, vb)
-            print(json.dumps({"epoch": epoch, "validation loss": val_loss}), flush=True)
+                if args.eval_fused:
+                    val_loss, vdict, vm = eval_epoch_fused(net, vb)
+                    vrec.update({"token accuracy": vm["token_accuracy"], "perplexity": vm["perplexity"]})
+                else:
+                    val_loss, vdict = eval_epoch(net, vb)
+            vrec["validation loss"] = val_loss
+            print(json.dumps(vrec), flush=True)
             if val_loss < min_val_loss and args.out_dir:
                 min_val_loss = val_loss
                 os.makedirs(args.out_dir, exist_ok=True)

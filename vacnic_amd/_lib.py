@@ -128,6 +128,11 @@ LmheadCeArgs = _struct("vacnic_lmhead_ce_args", [
     ("R", i64), ("V", i64), ("D", i64), ("ldh", i64), ("lde", i64), ("part_tiles", i64), ("ignore_index", i64),
     ("part_sum", vp), ("label_smoothing", f32)])
 
+LmheadEvalArgs = _struct("vacnic_lmhead_eval_args", [
+    ("h", vp), ("emb", vp), ("bias", vp), ("targets", vp), ("part", vp), ("part_arg", vp), ("tl", vp),
+    ("row_lse", vp), ("row_nll", vp), ("pred", vp), ("seq_nll", vp), ("seq_tokens", vp), ("seq_correct", vp), ("totals", vp),
+    ("R", i64), ("V", i64), ("D", i64), ("ldh", i64), ("lde", i64), ("part_tiles", i64), ("ignore_index", i64), ("rows_per_seq", i64)])
+
 BeamState = _struct("vacnic_beam_state", [
     ("seq0", vp), ("seq1", vp), ("beam_scores", vp), ("done", vp), ("hyp_cnt", vp), ("hyp_worst", vp), ("hyp_score", vp), ("hyp_len", vp),
     ("hyp_seq", vp), ("next_ids", vp), ("src_idx", vp), ("bans", vp),
@@ -196,6 +201,7 @@ _STRUCT_FNS = {
     "vacnic_name_embed_mean": NameEmbedArgs, "vacnic_adamw": AdamwArgs,
     "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_adamw_ema": AdamwEmaArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
     "vacnic_grad_guard": GradGuardArgs, "vacnic_param_stats": ParamStatsArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
+    "vacnic_lmhead_eval": LmheadEvalArgs,
     "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs,
 }
 _PLAIN_FNS = {

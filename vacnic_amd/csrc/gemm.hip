@@ -309,7 +309,7 @@ struct OnePlan {
 struct Dispatch { int n; vacnic_gemm_args args[2]; int hint[2]; };
 
 static int gemm_check_plan(const vacnic_gemm_args* a, int tile_hint, int ce_mode, OnePlan* o);
-static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0, bool ce_smooth = false);
+static int gemm_one(const vacnic_gemm_args* a, int hint, void* stream, int ce_mode = 0, int ce_col0 = 0, bool ce_smooth = false, bool ce_argmax = false);
 
 // A/B aid for whole-step measurements on ONE box (device-to-device spread is larger than most kernel deltas):
 // VACNIC_GEMM_DEBUG=<bits> is OR-ed into GemmP::debug of every launch (gemm_kernel.h: e.g. 16 = EPI_F32_STAGED everywhere)
@@ -507,7 +507,7 @@ static int gemm_check_plan(const vacnic_gemm_args* a, int tile_hint, int ce_mode
   return VACNIC_OK;
 }
 
-static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0, bool ce_smooth) {
+static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int ce_mode, int ce_col0, bool ce_smooth, bool ce_argmax) {
   OnePlan o;
   if (int e = gemm_check_plan(a, tile_hint, ce_mode, &o)) return e;
   GemmP p;
@@ -546,6 +546,7 @@ static int gemm_one(const vacnic_gemm_args* a, int tile_hint, void* stream, int 
     return launch_t64d(p, xk, wk, zsplits, s);
   }
   if (ce_mode && ce_smooth) return launch_t256cels(p, xk, wk, zsplits, s);   // label smoothing: its own kernel
+  if (ce_mode && ce_argmax) return launch_t256ceam(p, xk, wk, zsplits, s);   // evaluation head (argmax per tile): its own kernel
   if (ce_mode) return launch_t256ce(p, xk, wk, zsplits, s);
   switch (o.kernel) {
     case 260: return launch_t260(p, xk, wk, zsplits, s);
@@ -786,4 +787,121 @@ extern "C" int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t 
   g.out = dl; g.ldo = lddl;
   g.dact_src = a->targets; g.residual = rowp;
   return gemm_one(&g, 256 + 64000, stream, 4, (int)col0, smooth);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Fused validation head (vacnic_lmhead_eval): the forward GEMM above with the argmax epilogue (gemm_t256ceam.hip), then per row
+// {lse, nll, argmax} and per caption {nll, tokens, correct}; the logits are never written and nothing is an fp32 atomic, so every
+// output is bit-reproducible.  Teacher-forced scoring: no gradient, no label smoothing.
+namespace {
+// One wave per row.  The softmax merge is ce_combine_kernel's, statement for statement (row_lse is bit-identical to
+// vacnic_lmhead_ce_fwd's); the argmax merge takes the larger tile maximum (part[..][0], the value part_arg points at) and on
+// equal values the lower column.
+__global__ __launch_bounds__(256) void eval_combine_kernel(const float* __restrict__ part, const int* __restrict__ part_arg,
+                                                            const float* __restrict__ tl, const int64_t* __restrict__ targets,
+                                                            float* __restrict__ row_lse, float* __restrict__ row_nll,
+                                                            int64_t* __restrict__ pred, int R, int tiles, int64_t ignore) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = blockIdx.x * 4 + wave;
+  if (r >= R) return;                                   // (wave-uniform; no barrier below)
+  float mx = -INFINITY, sm = 0.f;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int t = lane; t < tiles; t += 64) {
+    const float pm = part[((size_t)r * tiles + t) * 2], ps = part[((size_t)r * tiles + t) * 2 + 1];
+    if (pm > -INFINITY) {
+      const float nm = fmaxf(mx, pm);
+      sm = (mx == -INFINITY ? 0.f : sm * __expf(mx - nm)) + ps * __expf(pm - nm);
+      mx = nm;
+    }
+    const int pi = part_arg[(size_t)r * tiles + t];
+    if (pm > bv || (pm == bv && pi < bi)) { bv = pm; bi = pi; }
+  }
+  const float gm = wave_max(mx);
+  const float gs = wave_sum(mx == -INFINITY ? 0.f : sm * __expf(mx - gm));
+  const float lse = gm + __logf(gs);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) {
+    row_lse[r] = lse;
+    row_nll[r] = targets[r] != ignore ? lse - tl[r] : 0.f;      // (tl[r] of an ignored row was never written)
+    pred[r] = bi;
+  }
+}
+
+// One wave per caption = rows [s * rps, (s + 1) * rps): lane l sums rows l, l + 64, ... in that order, then the xor butterfly —
+// a fixed order.  Ignored rows count nowhere (their row_nll is an exact 0).
+__global__ __launch_bounds__(256) void eval_seq_kernel(const float* __restrict__ row_nll, const int64_t* __restrict__ pred,
+                                                        const int64_t* __restrict__ targets, float* __restrict__ seq_nll,
+                                                        int* __restrict__ seq_tokens, int* __restrict__ seq_correct, int S, int rps,
+                                                        int64_t ignore) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.x * 4 + wave;
+  if (s >= S) return;
+  float nll = 0.f;
+  int tok = 0, cor = 0;
+  for (int i = lane; i < rps; i += 64) {
+    const size_t r = (size_t)s * rps + i;
+    const int64_t t = targets[r];
+    if (t != ignore) { nll += row_nll[r]; tok += 1; cor += pred[r] == t ? 1 : 0; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { nll += __shfl_xor(nll, o, 64); tok += __shfl_xor(tok, o, 64); cor += __shfl_xor(cor, o, 64); }
+  if (lane == 0) { seq_nll[s] = nll; seq_tokens[s] = tok; seq_correct[s] = cor; }
+}
+
+// totals[4] += {sum seq_nll, sum seq_tokens, sum seq_correct, S} in f64 by ONE workgroup: thread t adds the contiguous run of
+// captions [t * per, (t + 1) * per) in index order, thread 0 then adds the 256 runs in index order onto the running record.
+__global__ __launch_bounds__(256) void eval_totals_kernel(const float* __restrict__ seq_nll, const int* __restrict__ seq_tokens,
+                                                           const int* __restrict__ seq_correct, double* __restrict__ totals, int S) {
+  __shared__ double red[3][256];
+  const int per = (S + 255) / 256;
+  double nll = 0.0, tok = 0.0, cor = 0.0;
+  for (int s = threadIdx.x * per; s < min(S, (int)(threadIdx.x + 1) * per); ++s) { nll += (double)seq_nll[s]; tok += (double)seq_tokens[s]; cor += (double)seq_correct[s]; }
+  red[0][threadIdx.x] = nll; red[1][threadIdx.x] = tok; red[2][threadIdx.x] = cor;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nll = tok = cor = 0.0;
+    for (int t = 0; t < 256; ++t) { nll += red[0][t]; tok += red[1][t]; cor += red[2][t]; }
+    totals[0] += nll; totals[1] += tok; totals[2] += cor; totals[3] += (double)S;
+  }
+}
+}  // namespace
+
+extern "C" int vacnic_lmhead_eval(const vacnic_lmhead_eval_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_lmhead_eval, a, stream);
+  VCHECK(a && a->h && a->emb && a->targets && a->part && a->part_arg && a->tl && a->row_lse && a->row_nll && a->pred && a->seq_nll &&
+         a->seq_tokens && a->seq_correct, VACNIC_BAD_SHAPE, "lmhead_eval: null operand");
+  VCHECK(a->R > 0 && a->V > 0 && a->D > 0 && a->R < 0x7fffffffLL && a->V < 0x7fffffffLL, VACNIC_BAD_SHAPE, "lmhead_eval: empty problem");
+  VCHECK(a->rows_per_seq > 0 && a->R % a->rows_per_seq == 0, VACNIC_BAD_SHAPE, "lmhead_eval: R = %ld is not a multiple of rows_per_seq = %ld",
+         (long)a->R, (long)a->rows_per_seq);
+  const int64_t tiles = (a->V + 255) / 256;
+  VCHECK(a->part_tiles == tiles, VACNIC_BAD_SHAPE, "lmhead_eval: part_tiles must equal ceil(V / 256) = %ld (got %ld)", (long)tiles, (long)a->part_tiles);
+  hipStream_t st = (hipStream_t)stream;
+  vacnic_gemm_args g = vacnic_gemm_args{};
+  g.x = a->h; g.w = a->emb; g.bias = a->bias;
+  g.M = a->R; g.N = a->V; g.K = a->D;
+  g.ldx = a->ldh; g.ldw = a->lde;
+  g.alpha = 1.0f; g.split_k = 1;
+  g.out = a->part_arg;                   // the argmax epilogue writes the per-tile column indices through `out`
+  g.ldo = a->V;
+  g.preact = a->part; g.xsum = a->tl; g.dact_src = a->targets;
+  if (int e = gemm_one(&g, 256 + 64000, stream, 3, 0, false, true)) return e;
+  const dim3 rows4((unsigned)((a->R + 3) / 4));
+  hipLaunchKernelGGL(eval_combine_kernel, rows4, dim3(256), 0, st, a->part, a->part_arg, a->tl, a->targets, a->row_lse, a->row_nll,
+                     a->pred, (int)a->R, (int)tiles, a->ignore_index);
+  VLAUNCH_CHECK();
+  const int64_t S = a->R / a->rows_per_seq;
+  hipLaunchKernelGGL(eval_seq_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, st, a->row_nll, a->pred, a->targets, a->seq_nll,
+                     a->seq_tokens, a->seq_correct, (int)S, (int)a->rows_per_seq, a->ignore_index);
+  VLAUNCH_CHECK();
+  if (a->totals) {
+    hipLaunchKernelGGL(eval_totals_kernel, dim3(1), dim3(256), 0, st, a->seq_nll, a->seq_tokens, a->seq_correct, a->totals, (int)S);
+    VLAUNCH_CHECK();
+  }
+  return VACNIC_OK;
 }

@@ -402,9 +402,12 @@ __device__ __forceinline__ void p8_loop(f32x4 (&acc)[FB][FA], char* smem, __amdg
 // LS (with CE): the label-smoothing variants of the two cross-entropy epilogues (gemm_t256cels.hip) — again their own instantiation, so
 // that the CE kernels a run without smoothing launches stay exactly as they are.  Forward: additionally the sum of the tile's valid
 // logits -> part_sum[m][tn] (p.out).  Backward: p.residual holds FOUR floats per row {lse, coef, coef * (1 - eps), coef * eps / V}.
+// AM (with CE, forward only): the evaluation variant of the forward epilogue (gemm_t256ceam.hip) — once more its own instantiation, so
+// that the CE and LS kernels stay exactly as they are.  Additionally the global column index of the tile's largest valid logit (after
+// alpha and bias; ties to the lowest column) -> part_arg[m][tn] (p.out, int32).  Its value is the tile's softmax maximum part[m][tn][0].
 // One output tile: rows [m0, m0 + BM) x columns [n0, n0 + BN), reduction slice `zsplit`.  `tn` = this tile's column index inside
 // its row panel and p.tiles_n the number of tiles that share the panel (the xsum K-steps are dealt round-robin over them).
-template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false, bool LS = false, bool P8 = false>
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE, bool XKS, bool WKS, bool CE, bool DR = false, bool LS = false, bool P8 = false, bool AM = false>
 __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const int n0, const int tn, const int zsplit, const int tile_id = 0) {
   constexpr int NWAVE = WM * WN, NTHR = 64 * NWAVE;
   constexpr int TM = BM / WM, TN = BN / WN;             // per-wave output sub-tile
@@ -921,6 +924,25 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
             }
           }
         }
+        [[maybe_unused]] float av = -INFINITY;                // AM: the largest valid logit of this thread's columns and its column;
+        [[maybe_unused]] int ai = n0;                         // n0 is a valid column of every tile, so the index stays inside [0, N)
+        if constexpr (AM) {
+          // a pass of its own for the same reason as LS.  Only columns n < N take part: a pad column's logit is 0 (or the bias) and
+          // would win in a row whose real logits are all negative.  Ascending walk + strict `>`: ties go to the lowest column.
+#pragma unroll
+          for (int j0 = 0; j0 < CPT; j0 += 4) {
+            const f32x4 v4 = *(const f32x4*)(src + j0);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const int n = nb + j0 + j;
+              if (n < p.N) {
+                float v = v4[j] * p.alpha;
+                if (p.bias) v += p.bias[n];
+                if (v > av) { av = v; ai = n; }
+              }
+            }
+          }
+        }
 #pragma unroll
         for (int j0 = 0; j0 < CPT; j0 += 4) {
           const f32x4 v4 = *(const f32x4*)(src + j0);
@@ -945,10 +967,19 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int m0, const in
           mx = nm;
           if constexpr (LS) zs += __shfl_xor(zs, o, 64);
         }
+        if constexpr (AM) {
+#pragma unroll
+          for (int o = 1; o < TPR; o <<= 1) {                 // larger value, on equal values the lower column: every lane of the row agrees
+            const float ov = __shfl_xor(av, o, 64);
+            const int oi = __shfl_xor(ai, o, 64);
+            if (ov > av || (ov == av && oi < ai)) { av = ov; ai = oi; }
+          }
+        }
         if (seg == 0 && mok) {
           float* part = (float*)p.preact + ((size_t)m * p.tiles_n + tn) * 2;
           part[0] = mx; part[1] = sm;
           if constexpr (LS) ((float*)p.out)[(size_t)m * p.tiles_n + tn] = zs;
+          if constexpr (AM) ((int*)p.out)[(size_t)m * p.tiles_n + tn] = ai;
         }
       } else if (mok) {
         float lse, coef;
@@ -1111,6 +1142,17 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void gemm_ce_smooth_kernel(GemmP p
   gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, false, false, true, false, true>(p, tm * BM, tn * BN, tn, 0, bid);
 }
 
+// The cross-entropy forward kernel of the evaluation head (argmax epilogue, AM): the same tile walk again.
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+__global__ __launch_bounds__(64 * WM * WN, 2) void gemm_ce_argmax_kernel(GemmP p) {
+  if (p.debug & DBG_RETURN) return;
+  const int nt = p.tiles_m * p.tiles_n;
+  const int q = nt >> 3, r = nt & 7, xcd = blockIdx.x & 7;
+  const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
+  const int tm = bid / p.tiles_n, tn = bid - tm * p.tiles_n;
+  gemm_tile<BM, BN, WM, WN, BKT, NSTAGE, PIPE, false, false, true, false, false, false, true>(p, tm * BM, tn * BN, tn, 0, bid);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Grouped weight gradients: several independent dW[N,K] += dY[M,N]^T X[M,K] problems in ONE launch, no split-K.
 // A UNIT is a block of up to UT x UT output tiles of one problem with the FULL reduction; unit u runs on XCD u % 8 (workgroup L
@@ -1178,6 +1220,18 @@ int launch_gemm_ce_smooth(const GemmP& p0, bool xks, bool wks, int zsplits, hipS
 }
 
 template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
+int launch_gemm_ce_argmax(const GemmP& p0, bool xks, bool wks, int zsplits, hipStream_t s) {
+  if (xks || wks || zsplits != 1 || p0.out_mode != 3) { vacnic_set_error("gemm: the argmax epilogue is built for the cross-entropy forward (forward layout, no split-K)"); return VACNIC_UNSUPPORTED; }
+  GemmP p = p0;
+  p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (p.N + BN - 1) / BN;
+  constexpr size_t lds = NSTAGE * (BM + BN) * BKT * 2;
+  static_assert(lds >= 64 * (BN + 4) * 4, "epilogue staging must fit in the operand buffers");
+  launch_lds<gemm_ce_argmax_kernel<BM, BN, WM, WN, BKT, NSTAGE, PIPE>, lds>(dim3(p.tiles_m * p.tiles_n), dim3(64 * WM * WN), s, p);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+template <int BM, int BN, int WM, int WN, int BKT, int NSTAGE, bool PIPE>
 int launch_gemm_group(const GroupP& g, hipStream_t s) {
   static_assert(BM == 128 && BN == 128, "units are GROUP_UT x GROUP_UT tiles of 128 x 128");
   const int rounds = (g.nunits + 7) / 8;
@@ -1230,6 +1284,7 @@ int launch_t261(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t262(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t256ce(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s); // 256x256 ping-pong + LM-head cross-entropy epilogues
 int launch_t256cels(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s); // ... with the label-smoothing variants of those epilogues (LS)
+int launch_t256ceam(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s); // ... with the argmax forward epilogue of the evaluation head (AM)
 int launch_t256d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);  // the same tiles with the activation-dropout epilogues (DR)
 int launch_t264d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);
 int launch_t64d(const GemmP& p, bool xks, bool wks, int zsplits, hipStream_t s);

@@ -4,6 +4,7 @@ PyTorch here is plumbing only (device memory + the current HIP stream); every ar
 path is a hand-written gfx950 kernel in libvacnic_hip.so.  All wrappers launch on
 `torch.cuda.current_stream()` so they are hipGraph-capturable, and all fail loudly on CPU tensors.
 """
+import collections
 import contextlib
 import ctypes
 
@@ -484,6 +485,46 @@ def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1, label_smoothing=0.0, bi
                       label_smoothing=label_smoothing)
     _lib.check(_lib.lib.vacnic_lmhead_ce_fwd(_lib.C.byref(st), _stream()))
     return row_lse, acc
+
+
+LmheadEval = collections.namedtuple("LmheadEval", "row_lse row_nll pred seq_nll seq_tokens seq_correct")
+
+
+def lmhead_eval(h2, emb16, targets, V, rows_per_seq, ignore_index=1, bias=None, totals=None):
+    """fused validation head: ONE lm_head pass without logits -> LmheadEval(row_lse [R] f32 (bit-identical to lmhead_ce_fwd's),
+    row_nll [R] f32 (lse - target logit; exact 0 where target == ignore_index), pred [R] int64 (argmax over the V real columns, ties
+    to the lowest index), seq_nll [S] f32, seq_tokens [S] int32, seq_correct [S] int32) with S = R / rows_per_seq captions of
+    rows_per_seq consecutive rows each.  totals: optional float64 [4] running record {nll, tokens, correct, sequences} the call
+    ADDS its sums to (zero it once per validation pass with zero_()).  No fp32 atomics: every output is bit-reproducible.
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
+    R = h2.shape[0]
+    dev = h2.device
+    tiles = (V + 255) // 256
+    if totals is not None and (tuple(totals.shape) != (4,) or totals.dtype != torch.float64 or not totals.is_contiguous() or totals.device != dev):
+        raise ValueError(f"lmhead_eval: totals must be a contiguous float64 [4] tensor on {dev}")
+    S = R // rows_per_seq if rows_per_seq > 0 else 0                  # (a bad rows_per_seq is the library's to reject)
+    part = torch.empty((R, tiles, 2), device=dev, dtype=torch.float32)
+    part_arg = torch.empty((R, tiles), device=dev, dtype=torch.int32)
+    tl = torch.empty(R, device=dev, dtype=torch.float32)
+    out = LmheadEval(row_lse=torch.empty(R, device=dev, dtype=torch.float32), row_nll=torch.empty(R, device=dev, dtype=torch.float32),
+                     pred=torch.empty(R, device=dev, dtype=torch.int64), seq_nll=torch.empty(max(S, 1), device=dev, dtype=torch.float32)[:S],
+                     seq_tokens=torch.empty(max(S, 1), device=dev, dtype=torch.int32)[:S],
+                     seq_correct=torch.empty(max(S, 1), device=dev, dtype=torch.int32)[:S])
+    lmhead_eval_into(h2, emb16, targets, V, rows_per_seq, part, part_arg, tl, out, ignore_index=ignore_index, bias=bias, totals=totals)
+    return out
+
+
+def lmhead_eval_into(h2, emb16, targets, V, rows_per_seq, part, part_arg, tl, out, ignore_index=1, bias=None, totals=None, part_tiles=None):
+    """vacnic_lmhead_eval on caller-owned scratch (part, part_arg, tl) and outputs (an LmheadEval record): what a launch plan
+    records.  part_tiles: the tile count to declare (default ceil(V / 256), the only value the library accepts)."""
+    R, D = h2.shape
+    st = _lib.LmheadEvalArgs(h=_p(h2), emb=_p(emb16), bias=_p(bias), targets=_p(targets), part=_p(part), part_arg=_p(part_arg), tl=_p(tl),
+                             row_lse=_p(out.row_lse), row_nll=_p(out.row_nll), pred=_p(out.pred), seq_nll=_p(out.seq_nll),
+                             seq_tokens=_p(out.seq_tokens), seq_correct=_p(out.seq_correct), totals=_p(totals),
+                             R=R, V=V, D=D, ldh=h2.stride(0), lde=emb16.stride(0),
+                             part_tiles=(V + 255) // 256 if part_tiles is None else part_tiles, ignore_index=ignore_index,
+                             rows_per_seq=rows_per_seq)
+    _lib.check(_lib.lib.vacnic_lmhead_eval(_lib.C.byref(st), _stream()))
 
 
 def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0, V=None):

@@ -637,13 +637,27 @@ class BartForMultiModalGeneration(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, image_features=None, face_features=None,
                 face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, labels=None, output_logits=None,
-                encoder_outputs=None, output_attentions=None, label_smoothing=None, **unused):
+                encoder_outputs=None, output_attentions=None, label_smoothing=None, output_token_stats=None, token_totals=None,
+                **unused):
         """label_smoothing (None: config.label_smoothing) applies to the fused `labels=` loss only; 0.0 is the plain cross entropy.
+        output_token_stats=True (with labels=, under torch.no_grad() only: the statistics carry no graph; not together with
+        output_logits=True) scores the labels teacher-forced in ONE lm_head pass without logits (kernels.lmhead_eval):
+        out["token_stats"] = {token_logprobs [B, T] fp32 (0 at pad positions), pred_ids [B, T] int64 (greedy prediction at every
+        position), seq_logprob [B], seq_tokens [B], seq_correct [B]} and out["loss"] = -sum token_logprobs / tokens, the plain NLL
+        on the row_lse of the fused training loss (label_smoothing does not apply).  token_totals: optional float64 [4] running
+        record {nll, tokens, correct, captions} the pass adds its sums to (the caller zeroes it once per validation pass).
         output_attentions=True (None: config.output_attentions, MFULL:1944) adds the attention maps to the returned dict —
         see BartModel.forward.  They are the pre-dropout softmax, fp32, without an autograd graph.  generate() does not return
         maps."""
         if self.arena is None:
             raise RuntimeError("call model.finalize(device) before forward (parameters must live in the HBM arena)")
+        if output_token_stats:
+            if labels is None:
+                raise ValueError("output_token_stats=True scores `labels`: pass labels=")
+            if torch.is_grad_enabled():
+                raise ValueError("output_token_stats=True carries no autograd graph: call it under torch.no_grad() (or model.score)")
+            if output_logits:
+                raise ValueError("output_token_stats=True is the pass without logits: it cannot be combined with output_logits=True")
         if labels is not None and decoder_input_ids is None:
             _, decoder_input_ids = K.prep_ids(labels, self.config.pad_token_id, self.config.decoder_start_token_id, want_mask=False)
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, decoder_input_ids=decoder_input_ids,
@@ -651,6 +665,14 @@ class BartForMultiModalGeneration(nn.Module):
                          name_mask=name_mask, add_ner_ffn=add_ner_ffn, encoder_outputs=encoder_outputs,
                          output_attentions=output_attentions)
         h = out.pop("last_hidden_state")
+        if output_token_stats:
+            B, T = labels.shape
+            ev = K.lmhead_eval(ops._c(h).view(-1, h.shape[-1]), self.emb16_pad, ops._c(labels).view(-1), self.V, T,
+                               ignore_index=self.config.pad_token_id, totals=token_totals)
+            out["loss"] = (ev.seq_nll.sum(dtype=torch.float64) / ev.seq_tokens.sum().clamp(min=1)).float()
+            out["token_stats"] = {"token_logprobs": (0.0 - ev.row_nll).view(B, T), "pred_ids": ev.pred.view(B, T),
+                                  "seq_logprob": 0.0 - ev.seq_nll, "seq_tokens": ev.seq_tokens, "seq_correct": ev.seq_correct}
+            return out
         want_logits = output_logits if output_logits is not None else labels is None
         if labels is not None:
             hl, h = ops.fork(h) if want_logits else (h, None)
@@ -662,6 +684,19 @@ class BartForMultiModalGeneration(nn.Module):
             lg = ops.linear(h, self.model.shared.weight, self.s_lm)                           # lm_head(h) + final_logits_bias, MFULL:1997
             out["logits"] = lg
         return out
+
+    @torch.no_grad()
+    def score(self, input_ids=None, attention_mask=None, labels=None, **features):
+        """teacher-forced score of given captions under the current weights (e.g. generate(return_nbest=True) hypotheses under the
+        averaged weights): the `token_stats` record of forward(output_token_stats=True).  Runs in eval mode (no dropout) and
+        restores the mode.  features: image_features, face_features, ... as for forward."""
+        was_training = self.training
+        self.eval()
+        try:
+            return self(input_ids=input_ids, attention_mask=attention_mask, labels=labels, output_token_stats=True,
+                        **features)["token_stats"]
+        finally:
+            self.train(was_training)
 
     # ---- decoding (TRAIN:480-559, DDPINF:758-842 call model.generate) ----
     def generate(self, input_ids=None, attention_mask=None, **kw):

@@ -3,6 +3,7 @@ host syncs: ViT features -> multimodal BART (+ fused lm_head/CE) -> frozen guide
 SECLA -> backward -> DDP all-reduce -> fused AdamW with on-device linear-warmup schedule.
 """
 import contextlib
+import math
 from dataclasses import dataclass
 
 import torch
@@ -566,6 +567,89 @@ def eval_epoch(model, batches, device="cuda"):
         n += 1
     net.train(was_training)
     return val_loss / max(n, 1), out_dict
+
+
+def _scored_batches(net, batches, device, totals=None):
+    """the teacher-forced pass of eval_epoch over `batches` with the fused validation head: yields (target ids as the batch
+    delivered them, forward output) per batch; inputs are built exactly as eval_epoch builds them.  Nothing here waits for the
+    device."""
+    cfg = net.config
+    for batch in batches:
+        tgt_in_batch = batch["caption_ids"]
+        batch = to_device(batch, device)
+        src, src_mask, feats, kw = _model_inputs(net, batch)
+        tgt = batch["caption_ids"]
+        _, tgt_in = K.prep_ids(tgt, cfg.pad_token_id, start_id=cfg.eos_token_id)
+        out = net(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in, image_features=feats, labels=tgt,
+                  output_token_stats=True, token_totals=totals, add_ner_ffn=True, **kw)
+        yield tgt_in_batch, tgt, out
+
+
+def _ids_to_lists(tensors):
+    """nested lists of several [B, T] id tensors with ONE device-to-host copy (host tensors are read where they are)."""
+    on_dev = [t for t in tensors if t.is_cuda]
+    flat = torch.cat([t.reshape(-1) for t in on_dev]).cpu() if on_dev else None
+    out, pos = [], 0
+    for t in tensors:
+        if t.is_cuda:
+            out.append(flat[pos:pos + t.numel()].view(t.shape).tolist())
+            pos += t.numel()
+        else:
+            out.append(t.tolist())
+    return out
+
+
+@torch.no_grad()
+def eval_epoch_fused(model, batches, device="cuda"):
+    """eval_epoch with the fused validation head (model(..., output_token_stats=True)): ONE lm_head pass per batch instead of two,
+    no [B*T, V] logits, and no host sync per batch — losses, predicted ids and the running totals stay on the device and are
+    copied once after the last batch.  Returns (val_loss, out_dict, metrics): val_loss (mean of the per-batch plain-NLL losses)
+    and out_dict[step] = {"logit_output", "gt_cap"} mean what eval_epoch's mean; metrics = {"token_accuracy", "perplexity",
+    "tokens", "sequences"} over all batches (from the device-side totals: correct / tokens, exp(nll / tokens)) and
+    "seq_logprob", the teacher-forced log-likelihood of every sample's caption, in order."""
+    net = model.module if isinstance(model, DistributedDataParallel) else model
+    was_training = net.training
+    net.eval()
+    try:
+        totals = K.zero_(torch.empty(4, device=device, dtype=torch.float64))
+        losses, preds, gts, seq_lp = [], [], [], []
+        for tgt_host, tgt, out in _scored_batches(net, batches, device, totals):
+            losses.append(out["loss"])
+            preds.append(out["token_stats"]["pred_ids"])
+            gts.append(tgt_host if not tgt_host.is_cuda else tgt)
+            seq_lp.append(out["token_stats"]["seq_logprob"])
+        n = len(losses)
+        if n == 0:
+            return 0.0, {}, {"token_accuracy": 0.0, "perplexity": float("nan"), "tokens": 0, "sequences": 0, "seq_logprob": []}
+        nums = torch.cat([totals, torch.stack(losses).double()] + [s.double() for s in seq_lp]).tolist()      # the pass's one wait
+        lists = _ids_to_lists(preds + gts)
+    finally:
+        net.train(was_training)
+    nll, tokens, correct, sequences = nums[:4]
+    val_loss = 0.0
+    for v in nums[4:4 + n]:
+        val_loss += float(v)
+    out_dict = {step: {"logit_output": lists[step], "gt_cap": lists[n + step]} for step in range(n)}
+    metrics = {"token_accuracy": correct / max(tokens, 1.0), "perplexity": math.exp(nll / max(tokens, 1.0)), "tokens": int(tokens),
+               "sequences": int(sequences), "seq_logprob": nums[4 + n:]}
+    return val_loss / n, out_dict, metrics
+
+
+@torch.no_grad()
+def score_captions(model, batches, device="cuda"):
+    """teacher-forced scores of the captions in `batches` (inputs built as eval_epoch builds them) under the model's current
+    weights: {"logprob": [...], "tokens": [...], "correct": [...]}, one entry per sample in order — the caption's log-likelihood,
+    its number of non-pad tokens and how many of them the model predicts greedily.  One device-to-host copy at the end."""
+    net = model.module if isinstance(model, DistributedDataParallel) else model
+    was_training = net.training
+    net.eval()
+    try:
+        rows = [torch.stack([o["token_stats"]["seq_logprob"].double(), o["token_stats"]["seq_tokens"].double(),
+                             o["token_stats"]["seq_correct"].double()]) for _, _, o in _scored_batches(net, batches, device)]
+        cols = torch.cat(rows, 1).tolist() if rows else [[], [], []]
+    finally:
+        net.train(was_training)
+    return {"logprob": cols[0], "tokens": [int(v) for v in cols[1]], "correct": [int(v) for v in cols[2]]}
 
 
 @torch.no_grad()
