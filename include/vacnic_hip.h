@@ -254,6 +254,11 @@ typedef struct {
   int32_t defer_fold;                      /* 1 (with partials): leave the fold to the caller — vacnic_ln_partial_fold on a stream of
                                               its choice (the parameter gradients are needed only by AdamW / the reducer, so the fold
                                               need not sit in the backward chain) */
+  int32_t partials_any;                    /* 0 (a zero-initialised tail): as before, partials are used from 64 blocks (R >= 253) on and
+                                              fewer blocks add with atomics.  1 (the deterministic mode): partials are used for every
+                                              R >= 1, so that with defer_fold = 1 the kernel performs no atomic at all; the caller folds
+                                              rows = min(1024, ceil(R / 4)) with vacnic_fold_ordered.  Block b of the grid always owns
+                                              rows b * 4 + w + k * 4 * rows (wave w, k = 0, 1, ...): a function of R alone */
 } vacnic_add_ln_bwd_args;
 int vacnic_add_ln_bwd(const vacnic_add_ln_bwd_args* a, void* stream);
 /* dgamma[D] += sum over rows of partials[row][0][:], dbeta[D] += ... [row][1][:]  (partials f32 [rows][2][D], as written by
@@ -282,6 +287,44 @@ typedef struct {
   float p_drop; uint64_t seed; const uint64_t* seed_dev;
 } vacnic_embed_ln_bwd_args;
 int vacnic_embed_ln_bwd(const vacnic_embed_ln_bwd_args* a, void* stream);
+
+/*
+ * Fixed-order sums (the deterministic mode, vacnic_amd.ops.set_deterministic).  Every entry point below is a plain grid without
+ * atomics or hand-over between workgroups; every output element has one writer, which reads it, adds and writes it back, so two
+ * calls onto the same destination compose when they are ordered by their streams.  All additions are fp32, rounded one by one
+ * (no contraction), in the order given here — a function of the shapes alone.
+ *
+ * vacnic_fold_ordered: dst[c] += sum_b partials[b * ld + c] for c < cols; with dst2 also dst2[c] += sum_b partials[b * ld + cols + c].
+ *   Order (4 strands): s_w = +0; for b = w, w + 4, w + 8, ... < NB: s_w += partials[b][c];  t = ((s_0 + s_1) + s_2) + s_3;
+ *   dst[c] = dst[c] + t.  NB = 0 launches nothing.  VACNIC_BAD_SHAPE: dst null, cols <= 0, NB < 0, ld shorter than a row.
+ */
+int vacnic_fold_ordered(const float* partials, int64_t ld, float* dst, float* dst2, int64_t NB, int64_t cols, void* stream);
+/* dbias[n] += sum_m dy[m][n] (dy bf16 [M][ldy], ldy % 8 == 0) in two stages through partials f32 [partial_rows][N],
+ * partial_rows >= rows = vacnic_bias_grad_ordered_rows(M) = clamp(ceil(M / 64), 1, 256).  Stage 1: row block j owns rows
+ * [j * rpb, (j + 1) * rpb), rpb = ceil(M / rows); its strand g (of 4) adds rows j * rpb + g, + 4, ... in ascending order from +0 and
+ * partials[j][n] = ((g_0 + g_1) + g_2) + g_3.  Stage 2: vacnic_fold_ordered over the rows blocks. */
+int64_t vacnic_bias_grad_ordered_rows(int64_t M);
+int vacnic_bias_grad_ordered(const void* dy, float* dbias, int64_t M, int64_t N, int64_t ldy, float* partials, int64_t partial_rows,
+                             void* stream);
+/* src f32 [R][D] (D % 4 == 0, D <= 2048, 16-byte aligned), ids int64 [R]; either destination may be NULL.
+ *   dembed[id][:] = dembed[id][:] + scale * (src[r_0][:] + src[r_1][:] + ...) over the rows r_0 < r_1 < ... with ids[r] != padding_idx
+ *     and clamp(ids[r], 0, V - 1) == id (the clamp of vacnic_embed_ln_bwd), added in ascending r starting from src[r_0];
+ *   dpos[t + pos_offset][:] = dpos[..][:] + (src[t][:] + src[t + T][:] + src[t + 2T][:] + ...) for t < min(T, R), ascending.
+ * The product scale * sum is rounded before it is added (never an fma). */
+int vacnic_scatter_ordered(const float* src, const int64_t* ids, float* dembed, float* dpos, int64_t R, int64_t T, int64_t D, int64_t V,
+                           int64_t pos_offset, int64_t padding_idx, float scale, void* stream);
+/* vacnic_embed_ln_bwd without float atomics: every row's dh goes to dh_rows f32 [B T][D], the dgamma / dbeta sums of block b (rows
+ * b * 4 + w + k * 4 * rows) to partials f32 [partial_rows][2][D], partial_rows >= rows = min(1024, ceil(B T / 4)); then
+ * vacnic_scatter_ordered(dh_rows -> dembed, dpos) and vacnic_fold_ordered(partials -> dgamma, dbeta) on the same stream. */
+int vacnic_embed_ln_bwd_ordered(const vacnic_embed_ln_bwd_args* a, float* dh_rows, float* partials, int64_t partial_rows, void* stream);
+/* dst[0] = sum_i src[i] (n >= 0; overwrites).  Order (256 strands): s_t = +0; for i = t, t + 256, ... < n: s_t += src[i];
+ * total = +0; for t = 0 .. 255: total += s_t. */
+int vacnic_sum_ordered(const float* src, int64_t n, float* dst, void* stream);
+/* per-row loss terms of the fused LM head, from what vacnic_lmhead_ce_fwd left behind (row_lse, tl, and with label_smoothing > 0
+ * part_sum [R][part_tiles], part_tiles = ceil(V / 256)): row_loss[r] = row_lse[r] - tl[r] (+ eps * (tl[r] - mean_j z_j)), an exact 0
+ * where targets[r] == ignore_index.  vacnic_sum_ordered(row_loss, R, loss_sum) is the deterministic loss_sum. */
+int vacnic_lmhead_row_loss(const float* row_lse, const float* tl, const int64_t* targets, const float* part_sum, int64_t R, int64_t V,
+                           int64_t part_tiles, int64_t ignore_index, float label_smoothing, float* row_loss, void* stream);
 
 /*
  * Cross-entropy over materialised logits (CrossEntropyLoss(ignore_index=pad), TRAIN:287,816).

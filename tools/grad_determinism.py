@@ -1,6 +1,8 @@
 """Is one forward/backward bitwise reproducible?  N passes over the same batch with the same weights (dropout off): per-parameter
 count of gradient elements that differ from pass 0, the largest relative difference, and the loss vectors.  Small model of the DDP
-test by default; --full for configs[1] geometry at batch 4."""
+test by default; --full for configs[1] geometry at batch 4.  --deterministic: the passes run in ops.set_deterministic mode (every
+pass must then print "0 of N tensors differ"; with --trace the first differing call names a site the mode has missed);
+--dropout: the three hub dropouts at 0.1, same seeds and device counter before every pass."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,6 +14,9 @@ from vacnic_amd.training import TrainArgs, build_models, forward_losses
 def main(rank=0, world=1, port=0):
     side = "--no-streams" not in sys.argv
     streams.enable(side)
+    from vacnic_amd import ops
+    ops.set_deterministic("--deterministic" in sys.argv)
+    drop = 0.1 if "--dropout" in sys.argv else 0.0
     if world > 1:
         import torch.distributed as dist
         from vacnic_amd import ddp
@@ -19,7 +24,8 @@ def main(rank=0, world=1, port=0):
         torch.cuda.set_device(0)
         dist.init_process_group("gloo", rank=rank, world_size=world)
     cfg = VacnicConfig(d_model=768, encoder_layers=2, decoder_layers=2, encoder_attention_heads=12, decoder_attention_heads=12,
-                       encoder_ffn_dim=3072, decoder_ffn_dim=3072, enc_fusion_layer=[0], dim_common=768, clip_width=128, dropout=0.0)
+                       encoder_ffn_dim=3072, decoder_ffn_dim=3072, enc_fusion_layer=[0], dim_common=768, clip_width=128, dropout=drop,
+                       attention_dropout=drop, activation_dropout=drop)
     vcfg = ClipVisionConfig(width=128, layers=1, patch_size=16, image_size=32, output_dim=64)
     model, guide, _ = build_models(cfg, vcfg, init="synthetic", seed=3)
     model.train()
@@ -52,6 +58,9 @@ def main(rank=0, world=1, port=0):
         K.add_ln_bwd, K.gemm = ln, gm
     for i in range(6):
         net.arena.grad.zero_()
+        if drop:
+            ops.Rng.manual_seed(5)
+            ops.Rng.device_counter().zero_()
         total, out4, out = forward_losses(model, guide, batch, args)
         top = {"H": out["decoder_hidden_states"][-1].detach().clone()}
         out["decoder_hidden_states"][-1].register_hook(lambda g, top=top: top.__setitem__("dH", g.detach().clone()))
@@ -75,7 +84,7 @@ def main(rank=0, world=1, port=0):
         dist.destroy_process_group()
     if rank != 0:
         return
-    print("side streams", side)
+    print("side streams", side, "deterministic", ops.deterministic(), "dropout", drop)
     for i in range(1, len(tops)):
         msg = []
         for k in tops[0]:

@@ -109,6 +109,10 @@ parser.add_argument("--grad_stats_every", type=int, default=0, help="every N opt
 parser.add_argument("--grad_accum_steps", type=int, default=1, help="K batches per optimizer step: the gradients of K batches are "
                     "summed on the device and AdamW is applied to their mean, so one GPU reaches K times its batch size; the schedule "
                     "counts optimizer steps, an epoch uses a multiple of K batches; one process only")
+# deterministic mode (vacnic_amd.ops.set_deterministic); off by default
+parser.add_argument("--deterministic", default=False, type=_b, help="bitwise reproducible training steps in one process: every sum "
+                    "whose order depended on scheduling takes a fixed-order kernel instead of fp32 atomics (a debugging and "
+                    "regression mode: a few per cent slower)")
 # fused validation head (vacnic_amd.training.eval_epoch_fused); off by default = eval_epoch, as in the reference
 parser.add_argument("--eval_fused", default=False, type=_b, help="validate with one LM-head pass per batch that never writes the "
                     "logits and waits for the device once per pass; the epoch record gains the token accuracy and the perplexity")
@@ -165,7 +169,8 @@ def train_args(args, total_steps):
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
                      no_clip_norm=args.no_clip_norm, clip_norm=args.clip_norm,
                      no_decay_bias_ln=args.no_decay_bias_ln, lr_scale=tuple(scales), freeze=tuple(args.freeze),
-                     skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay, grad_stats_every=args.grad_stats_every)
+                     skip_nonfinite=args.skip_nonfinite, ema_decay=args.ema_decay, grad_stats_every=args.grad_stats_every,
+                     deterministic=bool(getattr(args, "deterministic", False)))
 
 
 def ema_eval(args):

@@ -83,7 +83,7 @@ AddLnBwdArgs = _struct("vacnic_add_ln_bwd_args", [
     ("dout", vp), ("x", vp), ("residual", vp), ("gamma", vp), ("mean", vp), ("rstd", vp),
     ("dresidual", vp), ("dx", vp), ("dgamma", vp), ("dbeta", vp),
     ("R", i64), ("D", i64), ("p_drop", f32), ("seed", u64), ("seed_dev", vp), ("partials", vp), ("partial_rows", i64),
-    ("defer_fold", i32)])
+    ("defer_fold", i32), ("partials_any", i32)])
 
 EmbedLnFwdArgs = _struct("vacnic_embed_ln_fwd_args", [
     ("ids", vp), ("embed", vp), ("pos", vp), ("gamma", vp), ("beta", vp), ("out", vp), ("mean", vp), ("rstd", vp),
@@ -238,6 +238,12 @@ _PLAIN_FNS = {
     "vacnic_plan_end": [i64], "vacnic_plan_replay": [i64, i64, i64], "vacnic_plan_destroy": [i64], "vacnic_stream_fence": [vp, vp],
     "vacnic_plan_pause": [i32],
     "vacnic_ln_partial_fold": [vp, vp, vp, i64, i64, vp],
+    "vacnic_fold_ordered": [vp, i64, vp, vp, i64, i64, vp],
+    "vacnic_bias_grad_ordered": [vp, vp, i64, i64, i64, vp, i64, vp],
+    "vacnic_scatter_ordered": [vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, f32, vp],
+    "vacnic_embed_ln_bwd_ordered": [C.POINTER(EmbedLnBwdArgs), vp, vp, i64, vp],
+    "vacnic_sum_ordered": [vp, i64, vp, vp],
+    "vacnic_lmhead_row_loss": [vp, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp],
     "vacnic_comm_load": [C.c_char_p], "vacnic_comm_unique_id": [vp], "vacnic_allreduce_bucket": [i64, vp, i64, i32, vp],
     "vacnic_comm_broadcast": [i64, vp, i64, i32, i32, vp], "vacnic_comm_destroy": [i64],
     "vacnic_event_record": [i32, vp], "vacnic_event_wait": [i32, vp],
@@ -247,7 +253,7 @@ EXPORTED = sorted(list(_STRUCT_FNS) + list(_PLAIN_FNS) + ["vacnic_last_error_str
                                                             "vacnic_plan_begin", "vacnic_plan_size", "vacnic_plan_mark",
                                                             "vacnic_gemm_workspace_bytes", "vacnic_gemm_counters", "vacnic_comm_init",
                                                             "vacnic_lmhead_topk_workspace", "vacnic_lmhead_topk_supported",
-                                                            "vacnic_param_stats_workspace_bytes"])
+                                                            "vacnic_param_stats_workspace_bytes", "vacnic_bias_grad_ordered_rows"])
 
 for _name, _st in _STRUCT_FNS.items():
     _fn = getattr(lib, _name)          # AttributeError here = stale .so: fail loudly
@@ -277,6 +283,8 @@ lib.vacnic_lmhead_topk_supported.restype = C.c_int32
 lib.vacnic_lmhead_topk_supported.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int32]
 lib.vacnic_param_stats_workspace_bytes.restype = C.c_int64
 lib.vacnic_param_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+lib.vacnic_bias_grad_ordered_rows.restype = C.c_int64
+lib.vacnic_bias_grad_ordered_rows.argtypes = [C.c_int64]
 lib.vacnic_gemm_workspace_bytes.restype = C.c_int64
 lib.vacnic_gemm_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int64]
 lib.vacnic_gemm_counters.restype = C.c_int64

@@ -319,15 +319,19 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
   }
 }
 
-template <int NCH>
-__global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ emb,
-                                                           const bf16_t* __restrict__ pos, const bf16_t* __restrict__ dout,
-                                                           const float* __restrict__ gamma, const float* __restrict__ mean_i,
-                                                           const float* __restrict__ rstd_i, float* __restrict__ demb,
-                                                           float* __restrict__ dpos, float* __restrict__ dgamma,
-                                                           float* __restrict__ dbeta, int64_t R, int T, int D, int64_t V,
-                                                           int pos_offset, float scale, int64_t padding_idx, float p_drop,
-                                                           uint64_t seed, const uint64_t* __restrict__ seed_dev) {
+// ORDERED (the deterministic mode's instantiation, a kernel of its own below): no float atomics.  `demb` is then the caller's fp32
+// scratch [R][D] that receives every row's dh (unscaled; pad rows too: dpos needs them), `dgamma` the scratch [gridDim.x][2][D]
+// that receives this block's dgamma / dbeta column sums; dpos / dbeta are not used.  vacnic_scatter_ordered and
+// vacnic_fold_ordered finish the job in a fixed order.
+template <int NCH, bool ORDERED>
+__device__ __forceinline__ void embed_ln_bwd_body(const int64_t* __restrict__ ids, const bf16_t* __restrict__ emb,
+                                                  const bf16_t* __restrict__ pos, const bf16_t* __restrict__ dout,
+                                                  const float* __restrict__ gamma, const float* __restrict__ mean_i,
+                                                  const float* __restrict__ rstd_i, float* __restrict__ demb,
+                                                  float* __restrict__ dpos, float* __restrict__ dgamma,
+                                                  float* __restrict__ dbeta, int64_t R, int T, int D, int64_t V,
+                                                  int pos_offset, float scale, int64_t padding_idx, float p_drop,
+                                                  uint64_t seed, const uint64_t* __restrict__ seed_dev) {
   __shared__ float stage[ROWS_PER_BLOCK][512];        // per-wave transpose buffer for the scatter-add
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -391,8 +395,12 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const int64_t* __rest
         const int col = 512 * i + e * 64 + lane;
         if (col < D) {
           const float dh = st[e * 64 + lane];
-          if (demb && !is_pad) atomicAdd(demb + id * D + col, dh * scale);
-          if (dpos) atomicAdd(dpos + (int64_t)t * D + col, dh);
+          if constexpr (ORDERED) {
+            demb[row * D + col] = dh;
+          } else {
+            if (demb && !is_pad) atomicAdd(demb + id * D + col, dh * scale);
+            if (dpos) atomicAdd(dpos + (int64_t)t * D + col, dh);
+          }
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -407,15 +415,46 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const int64_t* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) red[wave][lane * 8 + j] = pass == 0 ? dg[i][j] : db[i][j];
       __syncthreads();
-      float* dst = pass == 0 ? dgamma : dbeta;
-      if (dst) {
+      if constexpr (ORDERED) {
         for (int e = threadIdx.x; e < 512; e += 256) {
           const int c = (e >> 3) + 64 * i;
-          if (c < nchunk) atomicAdd(dst + c * 8 + (e & 7), red[0][e] + red[1][e] + red[2][e] + red[3][e]);
+          if (c < nchunk) dgamma[((size_t)blockIdx.x * 2 + pass) * D + c * 8 + (e & 7)] = red[0][e] + red[1][e] + red[2][e] + red[3][e];
+        }
+      } else {
+        float* dst = pass == 0 ? dgamma : dbeta;
+        if (dst) {
+          for (int e = threadIdx.x; e < 512; e += 256) {
+            const int c = (e >> 3) + 64 * i;
+            if (c < nchunk) atomicAdd(dst + c * 8 + (e & 7), red[0][e] + red[1][e] + red[2][e] + red[3][e]);
+          }
         }
       }
     }
   }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_ln_bwd_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ emb,
+                                                           const bf16_t* __restrict__ pos, const bf16_t* __restrict__ dout,
+                                                           const float* __restrict__ gamma, const float* __restrict__ mean_i,
+                                                           const float* __restrict__ rstd_i, float* __restrict__ demb,
+                                                           float* __restrict__ dpos, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, int64_t R, int T, int D, int64_t V,
+                                                           int pos_offset, float scale, int64_t padding_idx, float p_drop,
+                                                           uint64_t seed, const uint64_t* __restrict__ seed_dev) {
+  embed_ln_bwd_body<NCH, false>(ids, emb, pos, dout, gamma, mean_i, rstd_i, demb, dpos, dgamma, dbeta, R, T, D, V, pos_offset, scale,
+                                padding_idx, p_drop, seed, seed_dev);
+}
+template <int NCH>
+__global__ __launch_bounds__(256) void embed_ln_bwd_ordered_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ emb,
+                                                                   const bf16_t* __restrict__ pos, const bf16_t* __restrict__ dout,
+                                                                   const float* __restrict__ gamma, const float* __restrict__ mean_i,
+                                                                   const float* __restrict__ rstd_i, float* __restrict__ dh_rows,
+                                                                   float* __restrict__ partials, int64_t R, int T, int D, int64_t V,
+                                                                   int pos_offset, float scale, int64_t padding_idx, float p_drop,
+                                                                   uint64_t seed, const uint64_t* __restrict__ seed_dev) {
+  embed_ln_bwd_body<NCH, true>(ids, emb, pos, dout, gamma, mean_i, rstd_i, dh_rows, nullptr, partials, nullptr, R, T, D, V, pos_offset,
+                               scale, padding_idx, p_drop, seed, seed_dev);
 }
 
 // mean over Ln tokens of LN(embed*scale + pos): one wave per (b, name)
@@ -609,7 +648,8 @@ extern "C" int vacnic_add_ln_bwd(const vacnic_add_ln_bwd_args* a, void* stream) 
     int64_t nb = (a->R + 3) / 4;
     if (nb > 1024) nb = 1024;
     // two-stage dgamma/dbeta when the caller lends a scratch of >= nb rows and the atomics would collide (many blocks)
-    float* part = (a->partials && a->partial_rows >= nb && nb >= 64 && (a->dgamma || a->dbeta)) ? a->partials : nullptr;
+    // (partials_any, the deterministic mode: also below 64 blocks, where the default adds with atomics)
+    float* part = (a->partials && a->partial_rows >= nb && (nb >= 64 || a->partials_any) && (a->dgamma || a->dbeta)) ? a->partials : nullptr;
     switch (nch) {
       case 1: LAUNCH_LN_BWD(1, 4, nb); break;
       case 2: LAUNCH_LN_BWD(2, 4, nb); break;
@@ -667,6 +707,38 @@ extern "C" int vacnic_embed_ln_bwd(const vacnic_embed_ln_bwd_args* a, void* stre
                a->dgamma, a->dbeta, R, (int)a->T, (int)a->D, a->V, (int)a->pos_offset, a->embed_scale,
                a->padding_idx, a->p_drop, a->seed, a->seed_dev);
   VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+// The deterministic form of vacnic_embed_ln_bwd: the ORDERED kernel (same grid: block-to-row map a function of R alone), then the
+// ordered scatter of the dh rows and the ordered fold of the dgamma / dbeta block sums.
+extern "C" int vacnic_embed_ln_bwd_ordered(const vacnic_embed_ln_bwd_args* a, float* dh_rows, float* partials, int64_t partial_rows,
+                                           void* stream) {
+  VPLAN_REC_STRUCT(vacnic_embed_ln_bwd_ordered, a, dh_rows, partials, partial_rows, stream);
+  VCHECK(a && a->ids && a->embed && a->pos && a->dout && a->gamma && a->mean && a->rstd && dh_rows && partials, VACNIC_BAD_SHAPE,
+         "embed_ln_bwd_ordered: null operand");
+  if (int e = check_d(a->D, "embed_ln_bwd_ordered")) return e;
+  VCHECK(a->B >= 0 && a->T > 0 && a->V > 0, VACNIC_BAD_SHAPE, "embed_ln_bwd_ordered: bad shape B=%ld T=%ld V=%ld", (long)a->B, (long)a->T, (long)a->V);
+  VCHECK(aligned16(dh_rows) && aligned16(a->dembed) && aligned16(a->dpos), VACNIC_MISALIGNED,
+         "embed_ln_bwd_ordered: dh_rows / dembed / dpos must be 16-byte aligned");
+  const int64_t R = a->B * a->T;
+  if (R == 0) return VACNIC_OK;
+  int64_t nb = (R + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+  if (nb > 1024) nb = 1024;
+  VCHECK(partial_rows >= nb, VACNIC_BAD_SHAPE, "embed_ln_bwd_ordered: partials holds %ld rows, min(1024, ceil(B T / 4)) = %ld needed",
+         (long)partial_rows, (long)nb);
+  dim3 grid((unsigned)nb);
+  DISPATCH_NCH(nch_for(a->D), embed_ln_bwd_ordered_kernel, grid, (hipStream_t)stream, a->ids, (const bf16_t*)a->embed,
+               (const bf16_t*)a->pos, (const bf16_t*)a->dout, a->gamma, a->mean, a->rstd, dh_rows, partials, R, (int)a->T, (int)a->D, a->V,
+               (int)a->pos_offset, a->embed_scale, a->padding_idx, a->p_drop, a->seed, a->seed_dev);
+  VLAUNCH_CHECK();
+  if (a->dembed || a->dpos) {
+    if (int e = vacnic_scatter_ordered(dh_rows, a->ids, a->dembed, a->dpos, R, a->T, a->D, a->V, a->pos_offset, a->padding_idx,
+                                       a->embed_scale, stream)) return e;
+  }
+  if (a->dgamma && a->dbeta) return vacnic_fold_ordered(partials, 2 * a->D, a->dgamma, a->dbeta, nb, a->D, stream);
+  if (a->dgamma) return vacnic_fold_ordered(partials, 2 * a->D, a->dgamma, nullptr, nb, a->D, stream);
+  if (a->dbeta) return vacnic_fold_ordered(partials + a->D, 2 * a->D, a->dbeta, nullptr, nb, a->D, stream);
   return VACNIC_OK;
 }
 

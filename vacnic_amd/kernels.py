@@ -18,6 +18,9 @@ BF16 = torch.bfloat16
 
 
 _HAVE_GPU = None
+DETERMINISTIC = False     # ops.set_deterministic(): every fp32 sum whose order depended on scheduling takes a fixed-order kernel instead
+                          # (vacnic_*_ordered, include/vacnic_hip.h).  Read at launch time, so a launch plan replays the mode it was
+                          # recorded in.
 _OVERRIDE = None          # raw hipStream_t set by launch_on(): lets ops issue a few launches on a side stream without
                           # paying for torch.cuda.stream()'s context switch (~10 us of host time per use)
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -232,6 +235,8 @@ def gemm(x, w, M, N, K, *, bias=None, out=None, ldx=None, ldw=None, ldo=None, x_
                 split_k = t[1]
     if tile_hint < 0:
         tile_hint = 0
+    if DETERMINISTIC and out_mode == 2 and split_k > 1:
+        fixup = True                          # (fp32 atomics into `out` otherwise: the order of the K slices would be the scheduler's)
     st = _stream()
     ws = wsb = cnt = cntn = None
     if fixup and split_k > 1:
@@ -372,6 +377,23 @@ def add_ln_bwd(dout, x, residual, gamma, mean, rstd, dgamma, dbeta, p_drop=0.0, 
     else:
         dres = None            # identical to dx: caller reuses dx
     part, prow = None, 0
+    if DETERMINISTIC and dgamma is not None and dbeta is not None and R >= 1:
+        # every R through the per-block column sums (the kernel's block-to-row map depends on R alone) and the ordered fold: no atomic
+        # anywhere.  The fold stays off the backward chain when the caller names a stream for it; `part` (like dgamma / dbeta) is then
+        # on the side-stream keep-list until the compute stream has joined that stream (_p inside launch_on).
+        prow = min(1024, (R + 3) // 4)
+        part = torch.empty((prow, 2, D), device=x.device, dtype=torch.float32)
+        call_struct("vacnic_add_ln_bwd", stream=_stream(), dout=_p(dout), x=_p(x), residual=_p(residual), gamma=_p(gamma),
+                    mean=_p(mean), rstd=_p(rstd), dresidual=_p(dres), dx=_p(dx), dgamma=_p(dgamma), dbeta=_p(dbeta),
+                    R=R, D=D, p_drop=p_drop, seed=seed, seed_dev=_p(seed_dev), partials=_p(part), partial_rows=prow, defer_fold=1,
+                    partials_any=1)
+        if fold_on is not None and fold_on != _stream():
+            fence(_stream(), fold_on)
+            with launch_on(fold_on, fence=False):
+                fold_ordered(part, dgamma, dbeta, prow, D, ld=2 * D)
+        else:
+            fold_ordered(part, dgamma, dbeta, prow, D, ld=2 * D)
+        return dx, (dres if dres is not None else dx)
     if dgamma is not None and R >= 256:         # two-stage dgamma / dbeta reduction (below 256 rows: per-column atomics)
         prow = min(1024, (R + 3) // 4)
         part = torch.empty((prow, 2, D), device=x.device, dtype=torch.float32)     # scratch of the two-stage dgamma/dbeta fold
@@ -409,6 +431,17 @@ def embed_ln_bwd(ids, embed16, pos16, dout, gamma, mean, rstd, dembed, dpos, dga
                  pos_offset=2, padding_idx=1, p_drop=0.0, seed=0, seed_dev=None):
     B, T = ids.shape
     V, D = embed16.shape
+    if DETERMINISTIC and B * T > 0:
+        # no float atomics: dh rows to an fp32 scratch, then the ordered scatter (ascending row per id / position) and the ordered fold
+        prow = min(1024, (B * T + 3) // 4)
+        dh = torch.empty((B * T, D), device=ids.device, dtype=torch.float32)
+        part = torch.empty((prow, 2, D), device=ids.device, dtype=torch.float32)
+        st = _lib.EmbedLnBwdArgs(ids=_p(ids), embed=_p(embed16), pos=_p(pos16), dout=_p(dout), gamma=_p(gamma), mean=_p(mean),
+                                 rstd=_p(rstd), dembed=_p(dembed), dpos=_p(dpos), dgamma=_p(dgamma), dbeta=_p(dbeta), B=B, T=T, D=D, V=V,
+                                 pos_offset=pos_offset, embed_scale=embed_scale, padding_idx=padding_idx, p_drop=p_drop, seed=seed,
+                                 seed_dev=_p(seed_dev))
+        call("vacnic_embed_ln_bwd_ordered", ctypes.byref(st), _p(dh), _p(part), prow, _stream())
+        return
     call_struct("vacnic_embed_ln_bwd", stream=_stream(), ids=_p(ids), embed=_p(embed16), pos=_p(pos16), dout=_p(dout),
                 gamma=_p(gamma), mean=_p(mean), rstd=_p(rstd), dembed=_p(dembed), dpos=_p(dpos), dgamma=_p(dgamma),
                 dbeta=_p(dbeta), B=B, T=T, D=D, V=V, pos_offset=pos_offset, embed_scale=embed_scale,
@@ -431,12 +464,65 @@ def ce_fwd(logits, targets, V, ignore_index=1, label_smoothing=0.0):
     R, ldl = logits.shape[0], logits.stride(0)
     dev = logits.device
     row_lse = torch.empty(R, device=dev, dtype=torch.float32)
+    if DETERMINISTIC:
+        return _ce_fwd_ordered(logits, targets, V, ignore_index, label_smoothing, row_lse)[:2]
     acc = torch.zeros(2, device=dev, dtype=torch.float32)       # {loss_sum, count}
     call_struct("vacnic_ce_fwd", stream=_stream(), logits=_p(logits), targets=_p(targets), row_lse=_p(row_lse),
                 row_loss=None, loss_sum=acc.data_ptr(), count=acc.data_ptr() + 4, dlogits=None, grad_out=None,
                 grad_scale=1.0, R=R, V=V, ldl=ldl, ldd=ldl, ignore_index=ignore_index,
                 logits_f32=int(logits.dtype == torch.float32), label_smoothing=label_smoothing)
     return row_lse, acc
+
+
+def _ce_fwd_ordered(logits, targets, V, ignore_index, label_smoothing, row_lse):
+    """ce_fwd in the deterministic mode -> (row_lse, acc, row_loss): the same kernel writes its per-row loss terms (an exact 0 on
+    ignored rows) and adds its loss atomics into a word nobody reads; loss_sum is the ordered sum of the terms.  `count`, a sum of
+    1.0s, is exact in any order and stays the kernel's."""
+    R, ldl = logits.shape[0], logits.stride(0)
+    dev = logits.device
+    acc = zero_(torch.empty(4, device=dev, dtype=torch.float32))          # {loss_sum, count, the kernel's own atomic loss sum, -}
+    row_loss = torch.empty(R, device=dev, dtype=torch.float32)
+    call_struct("vacnic_ce_fwd", stream=_stream(), logits=_p(logits), targets=_p(targets), row_lse=_p(row_lse),
+                row_loss=_p(row_loss), loss_sum=acc.data_ptr() + 8, count=acc.data_ptr() + 4, dlogits=None, grad_out=None,
+                grad_scale=1.0, R=R, V=V, ldl=ldl, ldd=ldl, ignore_index=ignore_index,
+                logits_f32=int(logits.dtype == torch.float32), label_smoothing=label_smoothing)
+    sum_ordered(row_loss, acc)
+    return row_lse, acc, row_loss
+
+
+def sum_ordered(src, dst):
+    """dst[0] = sum of the fp32 vector src in the documented fixed order (vacnic_sum_ordered)."""
+    assert src.dtype == torch.float32 and src.is_contiguous() and dst.dtype == torch.float32
+    call("vacnic_sum_ordered", _p(src), src.numel(), _p(dst), _stream())
+
+
+def fold_ordered(partials, dst, dst2, NB, cols, ld=None):
+    """dst[c] += sum_b partials[b][c] (and dst2[c] += sum_b partials[b][cols + c]) in the documented fixed order, one writer per
+    element (vacnic_fold_ordered).  partials: fp32, rows `ld` floats apart (default: cols, or 2 cols with dst2)."""
+    if ld is None:
+        ld = cols * (2 if dst2 is not None else 1)
+    call("vacnic_fold_ordered", _p(partials), ld, _p(dst), _p(dst2), NB, cols, _stream())
+
+
+def bias_grad_ordered_rows(M):
+    """rows of the partials scratch of bias_grad_ordered for M rows of dy (host-side sizing: no GPU needed)."""
+    return int(_lib.lib.vacnic_bias_grad_ordered_rows(M))
+
+
+def bias_grad_ordered(dy2d, dbias, M, N, partials=None):
+    """dbias[n] += sum_m dy[m][n] without atomics: per-row-block column sums, then the ordered fold (vacnic_bias_grad_ordered)."""
+    rows = bias_grad_ordered_rows(M)
+    if partials is None:
+        partials = torch.empty((rows, max(N, 1)), device=dy2d.device, dtype=torch.float32)
+    call("vacnic_bias_grad_ordered", _p(dy2d), _p(dbias), M, N, dy2d.stride(0), _p(partials), partials.shape[0], _stream())
+
+
+def scatter_ordered(src, ids, dembed, dpos, T, V, pos_offset=2, padding_idx=1, scale=1.0):
+    """dembed[id] += scale * (sum of the rows of src with that id, ascending), dpos[t + pos_offset] += sum of rows t, t + T, ...
+    (vacnic_scatter_ordered); src fp32 [R, D], ids int64 [R]; either destination may be None."""
+    R, D = src.shape
+    assert src.dtype == torch.float32 and src.is_contiguous() and ids.dtype == torch.int64 and ids.numel() == R
+    call("vacnic_scatter_ordered", _p(src), _p(ids), _p(dembed), _p(dpos), R, T, D, V, pos_offset, padding_idx, float(scale), _stream())
 
 
 def ce_bwd(logits, targets, V, row_lse, acc, dlogits, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0):
@@ -481,10 +567,30 @@ def lmhead_ce_fwd(h2, emb16, targets, V, ignore_index=1, label_smoothing=0.0, bi
     if part_sum is not None and (tuple(part_sum.shape) != (R, tiles) or part_sum.dtype != torch.float32 or not part_sum.is_contiguous()
                                  or part_sum.device != dev):
         raise ValueError(f"lmhead_ce_fwd: part_sum must be a contiguous float32 [{R}, {tiles}] tensor on {dev}")
+    if DETERMINISTIC:
+        return lmhead_ce_fwd_ordered(h2, emb16, targets, V, part, tl, row_lse, ignore_index, label_smoothing, bias, part_sum)[:2]
     st = _lmhead_args(h2, emb16, targets, V, ignore_index, part, tl, row_lse, acc, bias=bias, part_sum=part_sum,
                       label_smoothing=label_smoothing)
     _lib.check(_lib.lib.vacnic_lmhead_ce_fwd(_lib.C.byref(st), _stream()))
     return row_lse, acc
+
+
+def lmhead_ce_fwd_ordered(h2, emb16, targets, V, part, tl, row_lse, ignore_index, label_smoothing, bias, part_sum):
+    """lmhead_ce_fwd in the deterministic mode -> (row_lse, acc, row_loss).  The forward entry point runs as it is (row_lse and
+    `count`, a sum of 1.0s, are its own: bit-identical) with its loss atomics pointed at a word nobody reads; the per-row loss terms
+    are then formed from what it left behind (vacnic_lmhead_row_loss) and summed in a fixed order into loss_sum."""
+    R = h2.shape[0]
+    dev = h2.device
+    acc = torch.empty(4, device=dev, dtype=torch.float32)                 # {loss_sum, count, the entry point's atomic loss sum, -}
+    row_loss = torch.empty(R, device=dev, dtype=torch.float32)
+    st = _lmhead_args(h2, emb16, targets, V, ignore_index, part, tl, row_lse, acc, bias=bias, part_sum=part_sum,
+                      label_smoothing=label_smoothing)
+    st.loss_sum = acc.data_ptr() + 8
+    _lib.check(_lib.lib.vacnic_lmhead_ce_fwd(_lib.C.byref(st), _stream()))
+    call("vacnic_lmhead_row_loss", _p(row_lse), _p(tl), _p(targets), _p(part_sum) if label_smoothing > 0.0 else None, R, V, (V + 255) // 256,
+         ignore_index, float(label_smoothing), _p(row_loss), _stream())
+    sum_ordered(row_loss, acc)
+    return row_lse, acc, row_loss
 
 
 LmheadEval = collections.namedtuple("LmheadEval", "row_lse row_nll pred seq_nll seq_tokens seq_correct")
@@ -860,6 +966,8 @@ def argmax_rows(logits, V):
 
 
 def bias_grad(dy2d, dbias, M, N):
+    if DETERMINISTIC:
+        return bias_grad_ordered(dy2d, dbias, M, N)
     call("vacnic_bias_grad", _p(dy2d), _p(dbias), M, N, dy2d.stride(0), _stream())
 
 

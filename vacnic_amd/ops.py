@@ -23,6 +23,30 @@ from . import streams
 BF16 = torch.bfloat16
 
 
+def set_deterministic(flag=True):
+    """Deterministic mode (off by default): one process's training step is then bitwise reproducible run to run — forward, backward
+    and optimizer, side streams on or off, eager or replayed from a launch plan.  Every fp32 sum whose order depended on scheduling
+    (LayerNorm / embedding / bias gradients, split-K weight gradients, loss_sum) takes a fixed-order kernel instead of atomics
+    (DESIGN.md §3 "deterministic mode"; what is not claimed: §8).  The mode is read when a kernel is launched, so a plan recorded in
+    one mode replays that mode."""
+    K.DETERMINISTIC = bool(flag)
+
+
+def deterministic():
+    return K.DETERMINISTIC
+
+
+@contextlib.contextmanager
+def deterministic_mode(flag=True):
+    """with ops.deterministic_mode(): ... — set_deterministic(flag) for the block, the previous setting afterwards."""
+    prev = K.DETERMINISTIC
+    K.DETERMINISTIC = bool(flag)
+    try:
+        yield
+    finally:
+        K.DETERMINISTIC = prev
+
+
 class Rng:
     """Dropout seeds: one fresh 64-bit seed per dropout site per step (Philox key); the kernels
     regenerate masks from (seed, element index) in backward, nothing is stored."""
@@ -184,7 +208,15 @@ class _WgradQueue:
         for _, _, sp in jobs:
             self.dst.discard(sp.wgrad.data_ptr())
         with _on_wgrad():                        # (every job fenced its producer -> wgrad stream when it was queued)
-            K.wgrad_group([(dy, x, sp.wgrad, sp.bgrad) for dy, x, sp in jobs])
+            if K.DETERMINISTIC:
+                # the grouped kernel deals the K-steps of its bias sums over the workgroups of a row panel, which then meet in
+                # atomics: the bias gradients take the ordered two-stage pass over dY instead (dW has one writer per element)
+                K.wgrad_group([(dy, x, sp.wgrad, None) for dy, x, sp in jobs])
+                for dy, _, sp in jobs:
+                    if sp.bgrad is not None:
+                        K.bias_grad_ordered(dy, sp.bgrad, M, sp.N)
+            else:
+                K.wgrad_group([(dy, x, sp.wgrad, sp.bgrad) for dy, x, sp in jobs])
         for _, _, sp in jobs:
             ddp.done(sp.wgrad, sp.bgrad)
 
@@ -248,6 +280,12 @@ def _wgrad_impl(dy2d, x2d, spec, M):
     N, Kd = spec.N, spec.K
     tiles = ((N + 127) // 128) * ((Kd + 127) // 128)
     split = K.wgrad_split(M, tiles)
+    xsum = spec.bgrad
+    if K.DETERMINISTIC and xsum is not None:
+        # xsum meets in fp32 atomics (its K-steps are dealt over several workgroups): the bias gradient takes a pass of its own over
+        # dY, in a fixed order; K.gemm sends every split-K weight gradient through the ordered fix-up in this mode
+        K.bias_grad_ordered(dy2d, xsum, M, N)
+        xsum = None
     # the bias gradient (column sums of dY) rides on the weight-gradient GEMM's own dY fragments (xsum): no second pass
     if split > 1 and M >= 4096:
         # split-K through the GEMM's ordered fix-up instead of fp32 atomics (bitwise reproducible dW); 256 x 256 tiles x 4 slices
@@ -258,10 +296,10 @@ def _wgrad_impl(dy2d, x2d, spec, M):
         if N >= 512 and Kd >= 512:
             hint, split = (128, 8) if N * Kd <= (1 << 20) else (256, 4)
         K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
-               x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad, fixup=True, tile_hint=hint)
+               x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=xsum, fixup=True, tile_hint=hint)
         return
     K.gemm(dy2d, x2d, N, Kd, M, out=spec.wgrad, ldx=dy2d.stride(0), ldw=x2d.stride(0), ldo=spec.wgrad.stride(0),
-           x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=spec.bgrad)
+           x_kstrided=True, w_kstrided=True, out_mode=2, split_k=split, xsum=xsum)
 
 
 # ------------------------------------------------------------------------------------------- Linear

@@ -41,6 +41,7 @@ class TrainArgs:
     ema_decay: float = 0.0                # --ema_decay: moving average of the weights inside the AdamW step (FusedAdamW); 0 = off
     grad_stats_every: int = 0             # --grad_stats_every N: per-parameter gradient / weight statistics every N steps (FusedAdamW)
     grad_accum_steps: int = 1             # --grad_accum_steps K: K batches per optimizer step (FusedAdamW(accum_steps=K)); one process
+    deterministic: bool = False           # --deterministic True: the step runs in ops.set_deterministic mode (bitwise reproducible run to run)
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -479,7 +480,11 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
 
 def train_step(model, guide, optimizer, batch, args: TrainArgs, ready=None, towers=None):
     """loss.backward(); optimizer.step(); scheduler.step(); zero_grad()  (TRAIN:364-374) — returns the device-side
-    loss vector {total, txt, secla, colam} WITHOUT syncing (the reference's four .item() calls per step are gone)."""
+    loss vector {total, txt, secla, colam} WITHOUT syncing (the reference's four .item() calls per step are gone).
+    args.deterministic: the step runs in ops.set_deterministic mode (so does a plan or a graph recorded from it)."""
+    if args.deterministic and not ops.deterministic():
+        with ops.deterministic_mode(True):
+            return train_step(model, guide, optimizer, batch, args, ready, towers)
     net = model.module if isinstance(model, DistributedDataParallel) else model
     if not net.training:
         net.train()
