@@ -665,6 +665,55 @@ int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token, void* str
 int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len,
                      void* stream);
 /*
+ * Sampling decode, one position (transformers 4.18 GenerationMixin.sample: processors on the raw logits, then the warpers
+ * temperature -> top-k -> top-p, then softmax and one draw) with the bookkeeping of the position: one launch, one workgroup per
+ * row, no host round trip.  Everything below is exact enough to be replayed on the host (tests/test_sample.py does).
+ *
+ * Inputs.  logits fp32 [R][ldl], the first V columns are real.  seq int32 [R][Lmax]: row r's history, cur_len tokens long
+ * (1 <= cur_len < Lmax).  done int32 [R].  params: 8 32-bit words of DEVICE memory, read at run time so that a captured launch
+ * serves every setting: [0] temperature T (f32)  [1] top_k (i32)  [2] top_p (f32)  [3] reserved  [4],[5] seed (low, high word)
+ * [6],[7] call counter (low, high word).  A T that is not > 0 is read as 1.
+ *
+ * Per row r, in this order:
+ * 1. Processors.  done[r] != 0: the row writes `pad` (log-prob 0) and nothing else happens to it.  forced_token >= 0: that token is
+ *    chosen with probability 1 (log-prob 0, kept = 1, thr = 0, mass = 1).  Otherwise token j becomes -inf if suppress_eos != 0 and
+ *    j == eos (MinLength), or, with n = no_repeat_ngram_size > 0 and cur_len + 1 >= n, if j == seq[r][i + n - 1] for some
+ *    0 <= i <= cur_len - n with seq[r][i .. i + n - 2] == seq[r][cur_len - n + 1 .. cur_len - 1] (NoRepeatNGram, computed from the
+ *    history in place).  A NaN logit counts as -inf, +inf as FLT_MAX.  A row without a finite logit left emits `eos`
+ *    (log-prob 0, kept = 0) and finishes.
+ * 2. Temperature.  z' = z / T: ONE IEEE-754 fp32 division, round to nearest even (not a multiplication by a reciprocal);
+ *    -0 is read as +0.
+ * 3. Top-k.  With 1 <= top_k < V: thr_k = the top_k-th largest z' counting duplicates and -inf entries; every z' >= thr_k stays,
+ *    so ties at the k-th value are all kept (HF: `scores < topk[-1]` is removed).  top_k <= 0 or >= V: off.  Integer radix select
+ *    over order-preserving keys: no floating-point arithmetic, the result is exact.
+ * 4. Top-p.  With 0 < top_p < 1, over the tokens left by step 3: q_v = rint(exp(z'_v - max z') * 2^31) as an integer (expf in fp32,
+ *    q = 0 for -inf), E_v = sum of q_w over the left tokens with z'_w > z'_v (STRICTLY larger), Zl = sum of all q_w.  Token v stays iff
+ *    E_v <= floor((double)top_p * (double)Zl).  The top token always stays; tokens of equal z' stay or go together, so the kept set
+ *    is {v : z'_v >= thr} for one threshold thr, found by a mass-weighted radix select over the whole row.  top_p >= 1 (or <= 0): off.
+ *    Without ties this is HF's TopPLogitsWarper (sort descending, drop where the cumulative probability BEFORE the token exceeds top_p).
+ * 5. Draw.  Philox4x32-10 with the 64-bit key K = seed + 0x9E3779B97F4A7C15 * call (mod 2^64; key word 0 = low half, word 1 = high
+ *    half) and the counter words (r, cur_len, 0x53414D50, 0).  m = output word 0 >> 8, u = (m + 0.5) * 2^-24 = (2 m + 1) / 2^25.
+ *    Over the kept FINITE tokens in ascending token id, with the integer masses q of step 4 (computed the same way when top-p is
+ *    off) and Z their sum: the token is the first whose inclusive cumulative mass c satisfies c * 2^25 > (2 m + 1) * Z.
+ *    All sums are integer sums, so they do not depend on the order they are formed in: two launches give the same bits, and there
+ *    is no floating-point atomic.  (The masses differ from exact probabilities by < 2^-32 of the top token's each, plus expf's error.)
+ * 6. Bookkeeping.  next_ids[r] (int64) = seq[r][cur_len] = token; done[r] = 1 if token == eos; logp[r][cur_len] (fp32 [R][Lmax],
+ *    may be NULL) = (z'_token - max z') - log(Z / 2^31), the log-probability under the distribution the token was drawn from.
+ *    Optional diagnostics (NULL = not written): kept[r] int32 = number of kept finite tokens; thr[r] = the threshold z' (-inf if
+ *    nothing was cut); mass[r] = Z / Zl (1 when top-p is off); u[r] = fp32(u), round to nearest even (written for every row).
+ *    u itself lies in (0, 1), but 2 m + 1 needs 25 bits once m >= 2^23 and fp32 holds 24: there the copy is rounded, and for
+ *    m = 2^24 - 1 it reads exactly 1.0.  Only this diagnostic is rounded: the draw compares the integers above.
+ * VACNIC_UNSUPPORTED: V outside [1, 65536].  VACNIC_BAD_SHAPE: a null operand, R < 1, ldl < V, cur_len outside [1, Lmax),
+ * forced_token >= V, a negative n-gram size.
+ */
+typedef struct {
+  const float* logits; const void* params; int32_t* seq; int32_t* done; int64_t* next_ids; float* logp;
+  int32_t* kept; float* thr; float* mass; float* u;
+  int64_t R, V, ldl, Lmax;
+  int32_t cur_len, eos, pad, no_repeat_ngram_size, suppress_eos, forced_token;
+} vacnic_sample_step_args;
+int vacnic_sample_step(const vacnic_sample_step_args* a, void* stream);
+/*
  * Persistent single-token decoder step: every BartDecoderLayer of one position (MFULL:793-890 with
  * past_key_value, eval mode: self-attention over the KV cache, cross-attention over the encoder K/V projected once, FFN, the
  * three post-LayerNorms) in ONE launch of max(d / 4, ffn / 16) co-resident workgroups.  The 8 phases of a layer hand their

@@ -144,6 +144,12 @@ LmheadTopkArgs = _struct("vacnic_lmhead_topk_args", [
     ("R", i64), ("V", i64), ("d", i64), ("ldw", i64), ("ldl", i64), ("workspace_floats", i64),
     ("n_ban", i32), ("eos", i32), ("suppress_eos", i32), ("forced_token", i32), ("K2", i32)])
 
+SampleStepArgs = _struct("vacnic_sample_step_args", [
+    ("logits", vp), ("params", vp), ("seq", vp), ("done", vp), ("next_ids", vp), ("logp", vp),
+    ("kept", vp), ("thr", vp), ("mass", vp), ("u", vp),
+    ("R", i64), ("V", i64), ("ldl", i64), ("Lmax", i64),
+    ("cur_len", i32), ("eos", i32), ("pad", i32), ("no_repeat_ngram_size", i32), ("suppress_eos", i32), ("forced_token", i32)])
+
 DecoderLayer = _struct("vacnic_decoder_layer", [
     ("w_kvq", vp), ("w_so", vp), ("w_cq", vp), ("w_co", vp), ("w_fc1", vp), ("w_fc2", vp),
     ("b_kvq", vp), ("b_so", vp), ("b_cq", vp), ("b_co", vp), ("b_fc1", vp), ("b_fc2", vp),
@@ -202,7 +208,7 @@ _STRUCT_FNS = {
     "vacnic_adamw_groups": AdamwGroupsArgs, "vacnic_adamw_ema": AdamwEmaArgs, "vacnic_grad_clip_coef_groups": GradClipGroupsArgs,
     "vacnic_grad_guard": GradGuardArgs, "vacnic_param_stats": ParamStatsArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
     "vacnic_lmhead_eval": LmheadEvalArgs,
-    "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs,
+    "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs, "vacnic_sample_step": SampleStepArgs,
 }
 _PLAIN_FNS = {
     "vacnic_combine_losses": [vp, vp, vp, vp, f32, f32, vp, vp],

@@ -11,6 +11,8 @@ What runs where
     NoRepeatNGram ban lists: `vacnic_beam_step`, one wave per batch item, in the same per-position graph; the
     host reads the state ONCE after the last position (and polls the done flags every 8th position to stop early).
     `device_beams=False` keeps the host-side scorer (one device->host copy of the [B*beams, 2*beams] candidates per token).
+  * sampling (`do_sample=True`, one beam): the same cached decoder, then the fp32 [rows, V] logits and `vacnic_sample_step` —
+    processors, temperature, top-k, top-p, one Philox draw, histories / done flags / log-probs — per position (SampleSession).
 
 The cache is preallocated ([layers, B*beams, max_length, 2d] bf16, k|v interleaved per row) instead of the reference's
 per-step torch.cat (MFULL:489-492).
@@ -471,6 +473,139 @@ class DecodeSession:
         return tv, ti
 
 
+class SampleSession:
+    """Device side of sampling decode for one shape (rows, S, max_length, logits-processor options): the cached decoder, the token
+    histories / log-probs / done flags, and one hipGraph per position t = {single-token decoder, LM-head logits, vacnic_sample_step}.
+    Temperature, top-k, top-p, seed and call counter live in an 8-word device buffer the kernel reads at run time, so the graphs of
+    a shape serve every setting.  As in DecodeSession the first caption runs eagerly and later ones replay."""
+
+    def __init__(self, model, R, S, max_length, ngram, min_length, forced_eos, eos, pad, forced_bos=None):
+        self.model, self.R, self.max_length = model, R, max_length
+        self.ngram, self.min_length, self.forced_eos, self.eos, self.pad, self.forced_bos = ngram, min_length, forced_eos, eos, pad, forced_bos
+        dev = model.emb16_pad.device
+        self.dec = CachedDecoder(model, R, S, max_length, reorders=False)
+        self.ids_s = torch.zeros((R, 1), device=dev, dtype=torch.long)
+        self.state = torch.zeros((2, R, max_length), device=dev, dtype=torch.int32)     # histories | log-probs: one copy out at the end
+        self.seq, self.logp = self.state[0], self.state[1].view(torch.float32)
+        self.done_d = torch.zeros(R, device=dev, dtype=torch.int32)
+        self.h_done = torch.zeros(R, dtype=torch.int32).pin_memory()
+        self.params = torch.zeros(8, device=dev, dtype=torch.int32)
+        self.h_params = torch.zeros(8, dtype=torch.int32).pin_memory()
+        self.graphs, self.pool, self.captions = {}, None, 0
+
+    def body(self, t):
+        cur_len = t + 1
+        forced = self.forced_eos if (self.forced_eos is not None and cur_len == self.max_length - 1) else -1
+        if self.forced_bos is not None and cur_len == 1:             # ForcedBOS runs before ForcedEOS, as in DecodeSession.body
+            forced = self.forced_bos if forced < 0 else forced
+        logits = self.dec.step(self.ids_s, t)
+        K.sample_step(logits, self.model.V, self.params, self.seq, self.done_d, self.ids_s, cur_len, logp=self.logp, eos=self.eos,
+                      pad=self.pad, no_repeat_ngram_size=self.ngram, suppress_eos=cur_len < self.min_length, forced_token=forced)
+
+    def run(self, start, use_graphs, temperature, top_k, top_p, seed, call):
+        """every position enqueued back to back; returns (tokens per row, histories int32 [R, L], log-probs fp32 [R, L]) on the host"""
+        K.sample_params(temperature, top_k, top_p, seed, call, out=self.h_params)
+        self.params.copy_(self.h_params, non_blocking=True)
+        self.state.zero_()
+        self.seq.fill_(self.pad)
+        self.seq[:, 0] = start
+        self.ids_s.fill_(start)
+        self.done_d.zero_()
+        steps, pending = 0, None
+        for t in range(self.max_length - 1):
+            if use_graphs and self.captions > 0:
+                g = self.graphs.get(t)
+                if g is None:
+                    g = torch.cuda.CUDAGraph()
+                    torch.cuda.synchronize()
+                    with K.capture_scope(("sample-session", id(self))), torch.cuda.graph(g, pool=self.pool):
+                        self.body(t)
+                    if self.pool is None:
+                        self.pool = g.pool()
+                    self.graphs[t] = g
+                g.replay()
+            else:
+                self.body(t)
+            steps = t + 1
+            # early stop as in DecodeSession.run_device: the done flags travel every 8th position and are looked at once they landed
+            if pending is not None and pending[0].query():
+                if bool(pending[1].all()):
+                    break
+                pending = None
+            if pending is None and t % 8 == 7 and t + 1 < self.max_length - 1:
+                self.h_done.copy_(self.done_d, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending = (ev, self.h_done)
+        host = self.state.cpu()
+        self.dec.check_step_kernel()
+        return steps + 1, host[0], host[1].view(torch.float32)
+
+
+_SAMPLE_CALLS = 0          # per-process count of generate(do_sample=True, seed=None) calls: successive calls draw differently
+_SAMPLE_SESSIONS_MAX = 8   # sampling sessions (KV cache, cross K/V, position graphs) a model keeps: rows = B * num_return_sequences is a
+                           # free axis of the key, so the least recently used session goes when a ninth shape arrives
+
+
+def _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_return_sequences):
+    if num_beams != 1:
+        raise ValueError(f"generate(do_sample=True): num_beams must be 1, got {num_beams} (beam-sample is not supported)")
+    if encoded is not None:
+        raise ValueError("generate(do_sample=True): encoded= (staged encoding) is not supported with sampling")
+    if not (isinstance(temperature, (int, float)) and temperature > 0 and temperature != float("inf")):
+        raise ValueError(f"generate(do_sample=True): temperature must be a finite number > 0, got {temperature!r}")
+    if not (isinstance(top_p, (int, float)) and 0 < top_p <= 1):
+        raise ValueError(f"generate(do_sample=True): top_p must be in (0, 1], got {top_p!r}")
+    if not (isinstance(top_k, int) and not isinstance(top_k, bool) and top_k >= 0):
+        raise ValueError(f"generate(do_sample=True): top_k must be an integer >= 0, got {top_k!r}")
+    if not (isinstance(num_return_sequences, int) and not isinstance(num_return_sequences, bool) and num_return_sequences >= 1):
+        raise ValueError(f"generate(do_sample=True): num_return_sequences must be an integer >= 1, got {num_return_sequences!r}")
+
+
+def _generate_sample(model, input_ids, attention_mask, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id,
+                     forced_bos_token_id, enc_args, add_ner_ffn, use_graphs, temperature, top_k, top_p, n, seed, return_logprobs):
+    """GenerationMixin.sample of transformers 4.18 (generate(do_sample=True, num_beams=1)): rows b * n + j = sample j of item b."""
+    global _SAMPLE_CALLS
+    cfg = model.config
+    eos, pad, start = cfg.eos_token_id, cfg.pad_token_id, cfg.decoder_start_token_id
+    if seed is None:
+        _SAMPLE_CALLS += 1
+        seed, call = torch.initial_seed(), _SAMPLE_CALLS
+    else:
+        seed, call = int(seed), 0
+    if max_length < 2:
+        raise ValueError(f"generate(do_sample=True): max_length must be >= 2, got {max_length}")
+    B = input_ids.shape[0]
+    R = B * n
+    mask_u8 = attention_mask.to(torch.uint8) if attention_mask.dtype != torch.uint8 else attention_mask
+    enc_h = _run_encoder(model, use_graphs, add_ner_ffn, input_ids, mask_u8, *enc_args)
+    S = enc_h.shape[1]
+    key = (R, S, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id)      # no T / top_k / top_p / seed
+    sessions = model.__dict__.setdefault("_sample_sessions", {})
+    ses = sessions.pop(key, None)
+    if ses is None:
+        while len(sessions) >= _SAMPLE_SESSIONS_MAX:
+            sessions.pop(next(iter(sessions)))           # (dicts keep insertion order: the first key is the least recently used)
+        ses = SampleSession(model, R, S, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id, eos, pad,
+                            forced_bos=forced_bos_token_id)
+    sessions[key] = ses                                  # most recently used last
+    ses.dec.begin(enc_h, mask_u8, n)
+    try:
+        cur_len, seqs, logps = ses.run(start, use_graphs, float(temperature), int(top_k), float(top_p), seed, call)
+    except Exception:
+        sessions.pop(key, None)                          # its graphs / buffers may hold a half-finished caption
+        raise
+    ses.captions += 1
+    seqs, logps = seqs[:, :cur_len], logps[:, :cur_len]
+    # a row ends at its first eos after the start token (everything behind it is pad, log-prob 0); L = the longest row
+    is_eos = seqs[:, 1:] == eos
+    ends = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 2, torch.full((R,), cur_len))
+    L = int(ends.max())
+    dev = model.emb16_pad.device
+    ids = seqs[:, :L].to(torch.long).to(dev)
+    return (ids, logps[:, :L].contiguous().to(dev)) if return_logprobs else ids
+
+
 def _run_encoder(model, use_graphs, add_ner_ffn, input_ids, mask_u8, image_features, name_ids, name_mask, face_features, face_mask):
     """the encoder pass of one generate() call: a hipGraph per input signature (GraphedCall) unless use_graphs is off"""
     def run_encoder(ids, m8, img, nids, nmask, faces, fmask, add_ner_ffn=add_ner_ffn):
@@ -544,7 +679,7 @@ class CaptionPipeline:
         """stage B (encoder stream): encoder + cross K/V of one caption into the EncodeStage, not before `after` (the previous caption's
         staged data have been copied into the decoder's buffers)"""
         src, src_mask, feats, kw = ent["inputs"]
-        if src.shape[0] != 1:
+        if src.shape[0] != 1 or self.gen_kw.get("do_sample"):          # (sampling decodes through the plain generate(): no staging)
             return
         with torch.cuda.stream(self.s_enc):
             self.s_enc.wait_event(ent["a"])
@@ -607,20 +742,40 @@ class CaptionPipeline:
 def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length=20, length_penalty=1.0, early_stopping=False,
              no_repeat_ngram_size=0, min_length=0, forced_eos_token_id="config", forced_bos_token_id=None, image_features=None,
              face_features=None, face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, use_graphs=True, device_beams=True,
-             return_nbest=False, encoded=None, _after_begin=None, **unused):
+             return_nbest=False, encoded=None, _after_begin=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
+             num_return_sequences=1, seed=None, return_logprobs=False, **unused):
     """GenerationMixin.generate(do_sample=False) semantics of transformers 4.18 for this model (greedy = 1 beam).
     Returns int64 [B, L] starting with decoder_start_token_id, padded with pad_token_id.
     Keyword defaults are the LIBRARY defaults; the defaults a hub checkpoint's config.json adds on top (what the reference's
     `model.generate(num_beams, max_length)` inherits after from_pretrained, TRAIN:513-520) are config.HUB_GENERATION_DEFAULTS and
     are passed explicitly by the trainer-level callers (training.gen_caption_from_loader_bart, utils/test_mmbart_clip_ddp.py).
     return_nbest: also return, per batch item, the finalized n-best list [(length-normalised score, ids)], best first — what
-    `num_return_sequences=num_beams, output_scores=True` exposes as sequences / sequences_scores (the bookkeeping of ALL beams)."""
+    `num_return_sequences=num_beams, output_scores=True` exposes as sequences / sequences_scores (the bookkeeping of ALL beams).
+
+    do_sample=True: GenerationMixin.sample instead (num_beams must be 1): logits processors, then temperature -> top_k -> top_p, then
+    one draw per row and position, all in vacnic_sample_step (include/vacnic_hip.h has the exact rules).  Returns int64
+    [B * num_return_sequences, L], row b * n + j = sample j of item b: start token, tokens, eos (drawn, or forced at
+    max_length - 1), then pad; with return_logprobs also fp32 [B * n, L], the log-probability of every token under the distribution
+    it was drawn from (0 at the start token and at padding).  seed: an int makes the call reproducible (same inputs, weights and
+    seed: same tokens, eager or replayed); None derives one from torch.initial_seed() and a per-process call counter.  With
+    do_sample=False these keywords are ignored."""
+    if do_sample:
+        _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_return_sequences)
     cfg = model.config
     if model.arena is None:
         raise RuntimeError("call model.finalize(device) first")
     was_training = model.training
     if was_training:
         model.eval()                              # (walks ~1000 modules: 1 ms — skipped when the model already is in eval mode)
+    if do_sample:
+        try:
+            return _generate_sample(model, input_ids, attention_mask, max_length, no_repeat_ngram_size, min_length,
+                                    cfg.eos_token_id if forced_eos_token_id == "config" else forced_eos_token_id, forced_bos_token_id,
+                                    (image_features, name_ids, name_mask, face_features, face_mask), add_ner_ffn, use_graphs,
+                                    temperature, top_k, top_p, num_return_sequences, seed, return_logprobs)
+        finally:
+            if was_training:
+                model.train()
     eos, pad, start = cfg.eos_token_id, cfg.pad_token_id, cfg.decoder_start_token_id
     if forced_eos_token_id == "config":
         forced_eos_token_id = eos                     # BartConfig default forced_eos_token_id=2

@@ -1004,6 +1004,30 @@ def lmhead_topk(h, emb, V, K_, *, bias=None, beam_scores=None, bans=None, eos=2,
     return tv, ti
 
 
+def sample_params(temperature=1.0, top_k=0, top_p=1.0, seed=0, call=0, out=None):
+    """the 8-word runtime parameter block of vacnic_sample_step (include/vacnic_hip.h) as a CPU int32 tensor: [T f32, top_k i32,
+    top_p f32, 0, seed low, seed high, call low, call high].  `out`: a (pinned) int32 [8] tensor to fill instead."""
+    import struct
+    seed, call = int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1)
+    words = struct.unpack("<8i", struct.pack("<fifiIIII", float(temperature), int(top_k), float(top_p), 0, seed & 0xFFFFFFFF, seed >> 32,
+                                             call & 0xFFFFFFFF, call >> 32))
+    out = torch.empty(8, dtype=torch.int32) if out is None else out
+    out.copy_(torch.tensor(words, dtype=torch.int32))
+    return out
+
+
+def sample_step(logits, V, params, seq, done, next_ids, cur_len, *, logp=None, eos=2, pad=1, no_repeat_ngram_size=0, suppress_eos=False,
+                forced_token=-1, kept=None, thr=None, mass=None, u=None):
+    """one position of sampling decode for every row: processors -> temperature -> top-k -> top-p -> one Philox draw, and the
+    bookkeeping (next_ids int64 [R], seq int32 [R, Lmax] at column cur_len, done int32 [R], logp fp32 [R, Lmax]) in one launch.
+    logits fp32 [R, >= V]; params: int32 [8] on the device (sample_params).  kept / thr / mass / u: optional per-row diagnostics."""
+    R = logits.shape[0]
+    call_struct("vacnic_sample_step", stream=_stream(), logits=_p(logits), params=_p(params), seq=_p(seq), done=_p(done), next_ids=_p(next_ids),
+                logp=_p(logp), kept=_p(kept), thr=_p(thr), mass=_p(mass), u=_p(u), R=R, V=V, ldl=logits.stride(0), Lmax=seq.shape[1],
+                cur_len=int(cur_len), eos=eos, pad=pad, no_repeat_ngram_size=no_repeat_ngram_size, suppress_eos=int(bool(suppress_eos)),
+                forced_token=forced_token)
+
+
 def image_u8_normalize(img_u8, flip=None, mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711)):
     """uint8 [B,3,H,W] (+ optional uint8 flip flags [B]) -> fp32 ToTensor + Normalize (TRAIN:741-764), bit-identical to torch."""
     B, C, H, W = img_u8.shape

@@ -664,7 +664,14 @@ def gen_caption_from_loader_bart(model, batches, beam_size, max_length, device="
     out_dict[step] = {"gt": target ids, "gen": generated ids} with `model.generate(num_beams=beam_size, max_length=max_length)`;
     `length_penalty` is the extra knob of the stand-alone generator (DDPINF:38,867).  Arguments the reference leaves to the model's
     config (no_repeat_ngram_size, early_stopping, forced BOS/EOS) default to the hub checkpoint's (config.HUB_GENERATION_DEFAULTS,
-    keyed by `plm_type`); `gen_kw` overrides them.  pipeline: overlap the next caption's encoder side with this caption's beam search."""
+    keyed by `plm_type`); `gen_kw` overrides them.  pipeline: overlap the next caption's encoder side with this caption's beam search.
+    Sampling: `do_sample=True, beam_size=1` with temperature / top_k / top_p / num_return_sequences / seed in `gen_kw` (generate());
+    "gen" then holds num_return_sequences rows per caption, and with return_logprobs=True "logprobs" their per-token log-probs."""
+    def entry(batch, gen):
+        if isinstance(gen, tuple):
+            return {"gt": batch["caption_ids"].tolist(), "gen": gen[0].tolist(), "logprobs": gen[1].tolist()}
+        return {"gt": batch["caption_ids"].tolist(), "gen": gen.tolist()}
+
     net = model.module if isinstance(model, DistributedDataParallel) else model
     was_training = net.training
     net.eval()
@@ -679,7 +686,7 @@ def gen_caption_from_loader_bart(model, batches, beam_size, max_length, device="
                                length_penalty=length_penalty, add_ner_ffn=True, **gkw)
         with torch.no_grad():
             for step, (batch, gen) in enumerate(pipe(to_device(b, device) for b in batches)):
-                out_dict[step] = {"gt": batch["caption_ids"].tolist(), "gen": gen.tolist()}
+                out_dict[step] = entry(batch, gen)
         net.train(was_training)
         return out_dict
     for step, batch in enumerate(batches):
@@ -687,7 +694,7 @@ def gen_caption_from_loader_bart(model, batches, beam_size, max_length, device="
         src, src_mask, feats, kw = _model_inputs(net, batch)
         gen = net.generate(input_ids=src, attention_mask=src_mask, num_beams=beam_size, max_length=max_length, image_features=feats,
                            length_penalty=length_penalty, add_ner_ffn=True, **kw, **gkw)
-        out_dict[step] = {"gt": batch["caption_ids"].tolist(), "gen": gen.tolist()}
+        out_dict[step] = entry(batch, gen)
     net.train(was_training)
     return out_dict
 
