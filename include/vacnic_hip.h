@@ -817,6 +817,40 @@ int vacnic_lmhead_ce_dlogits(const vacnic_lmhead_ce_args* a, int64_t col0, int64
                              const float* rowp, void* stream);
 
 /*
+ * Per-row weights on the fused LM head: loss = sum_r w_r l_r / N with w_r = weights[r / rows_per_weight] (rows_per_weight = 1: one
+ * weight per token; = T: one per caption of T consecutive rows) and l_r the row's loss term of the unweighted path.  The GEMMs are
+ * the unweighted ones: run vacnic_lmhead_ce_fwd as it is (its atomic loss_sum pointed at a word nobody reads), then
+ *   vacnic_lmhead_ce_wloss   from row_lse, tl and (label_smoothing > 0) part_sum [R][part_tiles] of that call:
+ *                            row_nll[r]   = l_r, the expression and tile-sum order of vacnic_lmhead_row_loss (bit-identical to its
+ *                                           row_loss; an exact 0 where targets[r] == ignore_index),
+ *                            row_wloss[r] = w_r * l_r, row_wnorm[r] = 1 (norm_mode 0, "tokens") or w_r (norm_mode 1, "weights"); both
+ *                                           0 on ignored rows,
+ *                            acc[0] = sum_r row_wloss[r], acc[1] = N = sum_r row_wnorm[r], each in the order of vacnic_sum_ordered
+ *                            (256 strands, then ascending).  N is the number of non-ignored rows (norm_mode 0) or the sum of their
+ *                            weights (norm_mode 1).
+ *   vacnic_lmhead_ce_rowp_w  the rowp of vacnic_lmhead_ce_dlogits, [R][2] for label_smoothing == 0, else [R][4] (16-byte aligned), with
+ *                            c = *norm, g = (grad_out ? *grad_out : 1) * grad_scale / c, coef = g * w_r in this order: w_r == 1.0f
+ *                            gives the bits of vacnic_lmhead_ce_rowp / _rowp_smooth.  coef (1 - eps) and coef eps / V are formed from
+ *                            that coef.  coef = 0 on ignored rows.  c is used as it is (no clamp to 1); c <= 0, NaN or inf makes every
+ *                            coefficient 0: no gradient, and no NaN in the gradient arena.
+ * loss = acc[0] / acc[1] (vacnic_combine_losses); 0 / 0 is NaN, like torch's mean over nothing.  Weights are any finite fp32 value,
+ * negative ones included (advantages are signed).  A row with w_r == 0 contributes exactly what an ignored row contributes under
+ * norm_mode 1; under norm_mode 0 it still counts as a token.  norm_mode 1 is meant for w >= 0.
+ * No floating-point atomics and no memset: both calls are bit-reproducible, in the default and in the deterministic mode alike, and
+ * record into launch plans and hipGraph captures.
+ * VACNIC_BAD_SHAPE before any launch: a null operand (part_sum may be NULL without smoothing, grad_out always), rows_per_weight < 1 or
+ * R % rows_per_weight != 0, norm_mode outside {0, 1}, label_smoothing outside [0, 1), smoothing without part_sum,
+ * part_tiles != ceil(V / 256).
+ */
+int vacnic_lmhead_ce_wloss(const float* row_lse, const float* tl, const int64_t* targets, const float* part_sum, const float* weights,
+                           int64_t rows_per_weight, int64_t R, int64_t V, int64_t part_tiles, int64_t ignore_index,
+                           float label_smoothing, int32_t norm_mode, float* row_nll, float* row_wloss, float* row_wnorm, float* acc,
+                           void* stream);
+int vacnic_lmhead_ce_rowp_w(const float* row_lse, const int64_t* targets, const float* weights, int64_t rows_per_weight,
+                            const float* norm, const float* grad_out, float grad_scale, float label_smoothing, int64_t V, float* rowp,
+                            int64_t R, int64_t ignore_index, void* stream);
+
+/*
  * Fused validation head: teacher-forced token log-probabilities, greedy predictions and per-caption sums from ONE LM-head pass,
  * again WITHOUT the [R, V] logits.  The forward GEMM of vacnic_lmhead_ce_fwd runs with a third epilogue (a kernel of its own; the
  * kernels vacnic_lmhead_ce_fwd launches are untouched): besides part[R][part_tiles][2] = {max, sum exp} and tl[R] it writes

@@ -116,6 +116,20 @@ parser.add_argument("--deterministic", default=False, type=_b, help="bitwise rep
 # fused validation head (vacnic_amd.training.eval_epoch_fused); off by default = eval_epoch, as in the reference
 parser.add_argument("--eval_fused", default=False, type=_b, help="validate with one LM-head pass per batch that never writes the "
                     "logits and waits for the device once per pass; the epoch record gains the token accuracy and the perplexity")
+# self-critical sequence training (vacnic_amd.training.self_critical_step) and the weighted text loss; off by default
+parser.add_argument("--scst_samples", type=int, default=0, help="N >= 2: every training step samples N captions per image on the "
+                    "device, scores them on the host (token-overlap F1 against the batch's caption) and minimises sum_c (reward_c - "
+                    "mean reward of the image) * NLL(sample_c) / tokens instead of the supervised losses; eager, one process, no "
+                    "--grad_accum_steps; 0 = off")
+parser.add_argument("--scst_ce_weight", type=float, default=0.0, help="with --scst_samples: the ground-truth captions join the same "
+                    "pass as rows of this weight (a cross-entropy anchor); 0 = sampled captions only")
+parser.add_argument("--scst_temperature", type=float, default=1.0, help="with --scst_samples: sampling temperature")
+parser.add_argument("--scst_top_k", type=int, default=0, help="with --scst_samples: keep the k most likely tokens (0 = all)")
+parser.add_argument("--scst_top_p", type=float, default=1.0, help="with --scst_samples: nucleus mass in (0, 1]")
+parser.add_argument("--scst_baseline", type=str, default="mean", choices=["mean", "leave_one_out"], help="with --scst_samples: what an "
+                    "image's reward is compared with: the mean of its N samples, or of the other N - 1")
+parser.add_argument("--loss_norm", type=str, default="tokens", choices=["tokens", "weights"], help="divisor of a weighted text loss "
+                    "(batches that carry 'loss_weights'): the number of non-pad tokens, or the sum of their weights")
 
 PLM = {"facebook/bart-base": dict(d_model=768, encoder_layers=6, decoder_layers=6, encoder_attention_heads=12,
                                   decoder_attention_heads=12, encoder_ffn_dim=3072, decoder_ffn_dim=3072),
@@ -150,7 +164,7 @@ def accum_epoch_steps(steps_per_epoch, accum_steps):
 def train_args(args, total_steps):
     """TrainArgs for the parsed flags.  total_steps: batches of the whole run; with --grad_accum_steps K the schedule gets the
     optimizer steps they make, total_steps // K."""
-    from vacnic_amd.training import TrainArgs
+    from vacnic_amd.training import TrainArgs, check_scst_flags
     scales = []
     for item in args.lr_scale:
         rx, sep, val = item.rpartition("=")
@@ -163,7 +177,8 @@ def train_args(args, total_steps):
         raise ValueError(f"--grad_stats_every {args.grad_stats_every!r}: expected a number of steps >= 1, or 0 for none")
     if args.grad_accum_steps < 1:
         raise ValueError(f"--grad_accum_steps {args.grad_accum_steps!r}: expected a number of batches >= 1")
-    return TrainArgs(lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
+    check_scst_flags(int(getattr(args, "scst_samples", 0)), args.grad_accum_steps)     # refused up front, before anything is built
+    return TrainArgs(loss_norm=getattr(args, "loss_norm", "tokens"),lr_bart=args.lr_bart, weight_decay=args.weight_decay, warmup_rate=args.warmup_rate,
                      num_training_steps=total_steps // args.grad_accum_steps, grad_accum_steps=args.grad_accum_steps,
                      margin=args.margin, alpha=args.alpha,
                      mapping_loss_weight=args.mapping_loss_weight, use_secla=args.use_secla, no_mapping=args.no_mapping,
@@ -184,7 +199,7 @@ def run(args, batches=None):
     from vacnic_amd import ops, streams, synthetic
     from vacnic_amd.ddp import DistributedDataParallel
     from vacnic_amd.training import (FusedAdamW, PlannedTrainStep, build_models, eval_epoch, eval_epoch_fused, gen_caption_from_loader_bart,
-                                     param_group_spec, to_device, train_step)
+                                     param_group_spec, to_device, train_step, check_scst_flags, self_critical_step)
 
     if not args.no_clip_loss or not args.freeze_clip:
         raise NotImplementedError("CLIP contrastive loss / CLIP fine-tuning are out of scope (SURVEY §2 row 20): pass --no_clip_loss True --freeze_clip True")
@@ -216,6 +231,8 @@ def run(args, batches=None):
         if steps_per_epoch <= 0:
             raise ValueError("the training shard holds fewer samples than one global batch")
     accum = int(args.grad_accum_steps)
+    scst = int(getattr(args, "scst_samples", 0))
+    check_scst_flags(scst, accum, world)                         # refused up front: no accumulated or data-parallel self-critical step
     if accum > 1:
         used = accum_epoch_steps(steps_per_epoch, accum)
         if used != steps_per_epoch and rank == 0:
@@ -285,7 +302,15 @@ def run(args, batches=None):
             else:
                 batch = to_device(batch, "cuda")
             g_ = guide if not args.only_image else None
-            if getattr(args, "launch_plan", True):
+            if scst:
+                # sample, score on the host, one weighted teacher-forced pass (eager: a host-side reward sits in its middle)
+                if ready is not None:
+                    torch.cuda.current_stream().wait_event(ready)
+                out4 = self_critical_step(net, opt, batch, targs, n_samples=scst, baseline=args.scst_baseline,
+                                          ce_weight=args.scst_ce_weight, seed=int(args.seed) * 1000003 + step,
+                                          temperature=args.scst_temperature, top_k=args.scst_top_k, top_p=args.scst_top_p,
+                                          max_length=int(args.caption_max_length))
+            elif getattr(args, "launch_plan", True):
                 # one recorded plan per batch geometry (a collated shard batch is padded to its own maxima): the first batch of a
                 # geometry runs eagerly, the second is recorded while it runs, later ones are one replay each; at most 4 plans are kept
                 # (each owns a private allocator pool)
@@ -313,6 +338,9 @@ def run(args, batches=None):
                 tot, txt, secla, colam = out4.tolist()
                 rec = {"step": step, "loss": tot, "text loss": txt, "face name loss": secla, "margin loss": colam,
                        "samples_per_s": round((step - start_step) * args.train_batch_size * world / (time.time() - t0), 2)}
+                if scst:                                            # self_critical_step's vector: other quantities in the four slots
+                    rec = {"step": step, "loss": tot, "mean reward": txt, "mean advantage^2": secla, "sampled token log-prob": colam,
+                           "samples_per_s": rec["samples_per_s"]}
                 if accum > 1:
                     rec["optimizer_step"] = opt.accum_report()["groups"]
                 if rep is not None:

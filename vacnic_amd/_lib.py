@@ -250,6 +250,8 @@ _PLAIN_FNS = {
     "vacnic_embed_ln_bwd_ordered": [C.POINTER(EmbedLnBwdArgs), vp, vp, i64, vp],
     "vacnic_sum_ordered": [vp, i64, vp, vp],
     "vacnic_lmhead_row_loss": [vp, vp, vp, vp, i64, i64, i64, i64, f32, vp, vp],
+    "vacnic_lmhead_ce_wloss": [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, f32, i32, vp, vp, vp, vp, vp],
+    "vacnic_lmhead_ce_rowp_w": [vp, vp, vp, i64, vp, vp, f32, f32, i64, vp, i64, i64, vp],
     "vacnic_comm_load": [C.c_char_p], "vacnic_comm_unique_id": [vp], "vacnic_allreduce_bucket": [i64, vp, i64, i32, vp],
     "vacnic_comm_broadcast": [i64, vp, i64, i32, i32, vp], "vacnic_comm_destroy": [i64],
     "vacnic_event_record": [i32, vp], "vacnic_event_wait": [i32, vp],

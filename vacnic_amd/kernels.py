@@ -593,6 +593,56 @@ def lmhead_ce_fwd_ordered(h2, emb16, targets, V, part, tl, row_lse, ignore_index
     return row_lse, acc, row_loss
 
 
+LOSS_NORMS = {"tokens": 0, "weights": 1}          # norm_mode of vacnic_lmhead_ce_wloss
+
+
+def check_loss_weights(who, weights, R, rows_per_weight, device, norm="tokens"):
+    """ValueError (naming the offending value) unless `weights` is what the weighted LM-head calls read: a contiguous float32 tensor
+    of R / rows_per_weight elements on `device`, and norm one of LOSS_NORMS.  Host-side only: nothing is launched."""
+    if norm not in LOSS_NORMS:
+        raise ValueError(f"{who}: norm={norm!r} is not one of {sorted(LOSS_NORMS)}")
+    if not isinstance(weights, torch.Tensor):
+        raise ValueError(f"{who}: weights must be a float32 tensor, got {type(weights).__name__}")
+    if weights.dtype != torch.float32:
+        raise ValueError(f"{who}: weights must be float32, got {weights.dtype}")
+    if weights.device != device:
+        raise ValueError(f"{who}: weights live on {weights.device}, the hidden states on {device}")
+    if not weights.is_contiguous():
+        raise ValueError(f"{who}: weights must be contiguous, got strides {tuple(weights.stride())} for shape {tuple(weights.shape)}")
+    if not isinstance(rows_per_weight, int) or rows_per_weight < 1 or R % rows_per_weight != 0:
+        raise ValueError(f"{who}: rows_per_weight={rows_per_weight!r} does not divide the {R} rows")
+    if weights.numel() != R // rows_per_weight:
+        raise ValueError(f"{who}: weights hold {weights.numel()} elements, {R} rows / rows_per_weight {rows_per_weight} need "
+                         f"{R // rows_per_weight}")
+
+
+def lmhead_ce_fwd_weighted(h2, emb16, targets, V, weights, rows_per_weight=1, norm="tokens", ignore_index=1, label_smoothing=0.0,
+                           bias=None):
+    """fused lm_head + weighted cross entropy forward without logits -> (row_lse [R], acc = {sum_r w_r l_r, N}, row_nll [R]) with
+    w_r = weights[r // rows_per_weight] (fp32, any sign), l_r the row's unweighted loss term (row_nll, an exact 0 on ignored rows)
+    and N the number of non-ignored rows (norm "tokens") or the sum of their weights (norm "weights").  loss = acc[0] / acc[1].
+    The forward entry point runs as it is, its atomics pointed at words nobody reads (as in lmhead_ce_fwd_ordered); the weighted
+    sums are formed from what it left behind in a fixed order (vacnic_lmhead_ce_wloss): the same bits in every run and mode.
+    Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
+    R = h2.shape[0]
+    dev = h2.device
+    check_loss_weights("lmhead_ce_fwd_weighted", weights, R, rows_per_weight, dev, norm)
+    tiles = (V + 255) // 256
+    part = torch.empty((R, tiles, 2), device=dev, dtype=torch.float32)
+    tl = torch.empty(R, device=dev, dtype=torch.float32)
+    row_lse = torch.empty(R, device=dev, dtype=torch.float32)
+    part_sum = torch.empty((R, tiles), device=dev, dtype=torch.float32) if label_smoothing > 0.0 else None
+    acc = torch.empty(4, device=dev, dtype=torch.float32)                 # {sum w l, N, the entry point's atomic loss sum, its count}
+    rows = torch.empty((3, R), device=dev, dtype=torch.float32)           # row_nll, row_wloss, row_wnorm
+    st = _lmhead_args(h2, emb16, targets, V, ignore_index, part, tl, row_lse, acc, bias=bias, part_sum=part_sum,
+                      label_smoothing=label_smoothing)
+    st.loss_sum, st.count = acc.data_ptr() + 8, acc.data_ptr() + 12
+    _lib.check(_lib.lib.vacnic_lmhead_ce_fwd(_lib.C.byref(st), _stream()))
+    call("vacnic_lmhead_ce_wloss", _p(row_lse), _p(tl), _p(targets), _p(part_sum), _p(weights), rows_per_weight, R, V, tiles, ignore_index,
+         float(label_smoothing), LOSS_NORMS[norm], _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(acc), _stream())
+    return row_lse, acc, rows[0]
+
+
 LmheadEval = collections.namedtuple("LmheadEval", "row_lse row_nll pred seq_nll seq_tokens seq_correct")
 
 
@@ -633,11 +683,22 @@ def lmhead_eval_into(h2, emb16, targets, V, rows_per_seq, part, part_arg, tl, ou
     _lib.check(_lib.lib.vacnic_lmhead_eval(_lib.C.byref(st), _stream()))
 
 
-def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0, V=None):
+def lmhead_ce_rowp(row_lse, targets, acc, grad_out=None, grad_scale=1.0, ignore_index=1, label_smoothing=0.0, V=None, weights=None,
+                   rows_per_weight=1):
     """per-row operands of lmhead_ce_dlogits: [R, 2] = {lse, coef}; with label_smoothing > 0 (which needs V) [R, 4] =
     {lse, coef, coef (1 - eps), coef eps / V}.  Pass the same label_smoothing to lmhead_ce_dlogits.
+    weights (fp32 [R / rows_per_weight], with the acc of lmhead_ce_fwd_weighted): coef = (grad_out grad_scale / acc[1]) * w_r, acc[1]
+    used as it is; acc[1] <= 0 or non-finite gives all-zero coefficients (vacnic_lmhead_ce_rowp_w).
     Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
     R = row_lse.shape[0]
+    if weights is not None:
+        check_loss_weights("lmhead_ce_rowp", weights, R, rows_per_weight, row_lse.device)
+        if label_smoothing != 0.0 and V is None:
+            raise TypeError("lmhead_ce_rowp: label_smoothing needs V (the uniform term is eps / V)")
+        rowp = torch.empty((R, 4 if label_smoothing > 0.0 else 2), device=row_lse.device, dtype=torch.float32)
+        call("vacnic_lmhead_ce_rowp_w", _p(row_lse), _p(targets), _p(weights), rows_per_weight, acc.data_ptr() + 4, _p(grad_out), grad_scale,
+             float(label_smoothing), 1 if V is None else V, _p(rowp), R, ignore_index, _stream())
+        return rowp
     if label_smoothing != 0.0:
         if V is None:
             raise TypeError("lmhead_ce_rowp: label_smoothing needs V (the uniform term is eps / V)")

@@ -638,8 +638,13 @@ class BartForMultiModalGeneration(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, decoder_input_ids=None, image_features=None, face_features=None,
                 face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, labels=None, output_logits=None,
                 encoder_outputs=None, output_attentions=None, label_smoothing=None, output_token_stats=None, token_totals=None,
-                **unused):
+                loss_weights=None, loss_norm="tokens", **unused):
         """label_smoothing (None: config.label_smoothing) applies to the fused `labels=` loss only; 0.0 is the plain cross entropy.
+        loss_weights (with labels=; fp32 [B], one weight per caption, or [B, T], one per token; any sign, no gradient) makes
+        out["loss"] = sum w l / N over the non-pad tokens, N their number (loss_norm="tokens") or the sum of their weights
+        (loss_norm="weights"); out["loss_acc"] = {sum w l, N} and out["token_nll"] [B, T] fp32 holds the unweighted per-token
+        terms l (0 at pad positions, no graph).  Only the fused loss is weighted: output_logits=True returns the logits as always.
+        Not together with output_token_stats=True (the validation loss stays the plain NLL).
         output_token_stats=True (with labels=, under torch.no_grad() only: the statistics carry no graph; not together with
         output_logits=True) scores the labels teacher-forced in ONE lm_head pass without logits (kernels.lmhead_eval):
         out["token_stats"] = {token_logprobs [B, T] fp32 (0 at pad positions), pred_ids [B, T] int64 (greedy prediction at every
@@ -658,6 +663,15 @@ class BartForMultiModalGeneration(nn.Module):
                 raise ValueError("output_token_stats=True carries no autograd graph: call it under torch.no_grad() (or model.score)")
             if output_logits:
                 raise ValueError("output_token_stats=True is the pass without logits: it cannot be combined with output_logits=True")
+        if loss_weights is not None:
+            if labels is None:
+                raise ValueError("loss_weights weigh the fused `labels=` loss: pass labels=")
+            if output_token_stats:
+                raise ValueError("loss_weights cannot be combined with output_token_stats=True: the validation pass is unweighted")
+            B, T = labels.shape
+            if tuple(loss_weights.shape) not in ((B,), (B, T)):
+                raise ValueError(f"loss_weights has shape {tuple(loss_weights.shape)}: [B] = ({B},) per caption or [B, T] = ({B}, {T}) "
+                                 "per token")
         if labels is not None and decoder_input_ids is None:
             _, decoder_input_ids = K.prep_ids(labels, self.config.pad_token_id, self.config.decoder_start_token_id, want_mask=False)
         out = self.model(input_ids=input_ids, attention_mask=attention_mask, decoder_input_ids=decoder_input_ids,
@@ -676,9 +690,15 @@ class BartForMultiModalGeneration(nn.Module):
         want_logits = output_logits if output_logits is not None else labels is None
         if labels is not None:
             hl, h = ops.fork(h) if want_logits else (h, None)
-            loss, acc = ops.lm_head_ce(hl, self.model.shared.weight, self.emb16_pad, self.model.shared.weight.grad, labels,
-                                       self.V, self.config.pad_token_id,
-                                       label_smoothing=self.config.label_smoothing if label_smoothing is None else label_smoothing)
+            eps = self.config.label_smoothing if label_smoothing is None else label_smoothing
+            if loss_weights is None:
+                loss, acc = ops.lm_head_ce(hl, self.model.shared.weight, self.emb16_pad, self.model.shared.weight.grad, labels,
+                                           self.V, self.config.pad_token_id, label_smoothing=eps)
+            else:
+                loss, acc, nll = ops.lm_head_ce(hl, self.model.shared.weight, self.emb16_pad, self.model.shared.weight.grad, labels,
+                                                self.V, self.config.pad_token_id, label_smoothing=eps, weights=loss_weights,
+                                                rows_per_weight=T if loss_weights.dim() == 1 else 1, norm=loss_norm)
+                out["token_nll"] = nll.view(B, T)
             out["loss"], out["loss_acc"] = loss, acc
         if want_logits:
             lg = ops.linear(h, self.model.shared.weight, self.s_lm)                           # lm_head(h) + final_logits_bias, MFULL:1997

@@ -775,24 +775,36 @@ class LmHeadCeFn(Function):
     (into the tied matrix's gradient rows) GEMMs before the buffer is re-used."""
 
     @staticmethod
-    def forward(ctx, h, anchor, emb16_pad, egrad, targets, V, ignore_index, ge, label_smoothing=0.0):
+    def forward(ctx, h, anchor, emb16_pad, egrad, targets, V, ignore_index, ge, label_smoothing=0.0, weights=None, rows_per_weight=1,
+                norm="tokens"):
         _tag(ctx)
         d = h.shape[-1]
         h2 = _c(h).view(-1, d)
         tgt = _c(targets).view(-1)
-        row_lse, acc = K.lmhead_ce_fwd(h2, emb16_pad, tgt, V, ignore_index=ignore_index, label_smoothing=label_smoothing)
+        row_nll = None
+        if weights is None:
+            row_lse, acc = K.lmhead_ce_fwd(h2, emb16_pad, tgt, V, ignore_index=ignore_index, label_smoothing=label_smoothing)
+        else:                     # loss = sum_r w_r l_r / N: the same GEMM, the sums in a fixed order (kernels.lmhead_ce_fwd_weighted)
+            row_lse, acc, row_nll = K.lmhead_ce_fwd_weighted(h2, emb16_pad, tgt, V, weights, rows_per_weight, norm,
+                                                             ignore_index=ignore_index, label_smoothing=label_smoothing)
         out4 = K.combine_losses(acc.data_ptr(), acc.data_ptr() + 4, None, None, 0.0, 0.0, h.device)
         ctx.misc = (emb16_pad, egrad, V, ignore_index, h2.shape[0], d, h.shape, label_smoothing)
+        ctx.weights = (weights, rows_per_weight)                       # data, not a differentiable input: kept beside the graph
         ctx.save_for_backward(h2, tgt, row_lse, acc)
-        ctx.mark_non_differentiable(acc)
         ddp.expect(ge and any(ctx.needs_input_grad), egrad)
-        return out4[1], acc
+        if weights is None:
+            ctx.mark_non_differentiable(acc)
+            return out4[1], acc
+        ctx.mark_non_differentiable(acc, row_nll)
+        return out4[1], acc, row_nll
 
     @_bw
-    def backward(ctx, g, _gacc):
+    def backward(ctx, g, _gacc, _gnll=None):
         h2, tgt, row_lse, acc = ctx.saved_tensors
         emb16_pad, egrad, V, ignore_index, R, d, hshape, eps = ctx.misc
-        rowp = K.lmhead_ce_rowp(row_lse, tgt, acc, grad_out=_c(g), grad_scale=1.0, ignore_index=ignore_index, label_smoothing=eps, V=V)
+        weights, rows_per_weight = ctx.weights
+        rowp = K.lmhead_ce_rowp(row_lse, tgt, acc, grad_out=_c(g), grad_scale=1.0, ignore_index=ignore_index, label_smoothing=eps, V=V,
+                                weights=weights, rows_per_weight=rows_per_weight)
         CH = min(LMHEAD_CHUNK, (V + 7) // 8 * 8)
         # dE (the tied matrix's weight gradient) is needed only by AdamW / the reducer: with side streams on it runs on the
         # weight-gradient stream beside the next chunk's dlogits / dh GEMMs, out of the decoder phase's chain (the least busy part of
@@ -819,14 +831,26 @@ class LmHeadCeFn(Function):
                            split_k=K.wgrad_split(R, tiles))
         dh = K.cast_f32_bf16(dh32)
         ddp.done(egrad)
-        return dh.view(hshape), None, None, None, None, None, None, None, None
+        return (dh.view(hshape),) + (None,) * (8 if weights is None else 11)
 
 
-def lm_head_ce(h, anchor, emb16_pad, egrad, targets, V, ignore_index=1, label_smoothing=0.0):
+def lm_head_ce(h, anchor, emb16_pad, egrad, targets, V, ignore_index=1, label_smoothing=0.0, weights=None, rows_per_weight=1,
+               norm="tokens"):
     """label_smoothing: torch's CrossEntropyLoss(label_smoothing=); 0.0 = the plain loss, bit-identical to the path without the option.
+    weights (fp32, contiguous, on h's device, no gradient): loss = sum_r w_r l_r / N with w_r = weights.view(-1)[r // rows_per_weight]
+    over the R = h.numel() / d rows — rows_per_weight=1 is one weight per token, =T one per caption — and N the number of
+    non-ignored rows (norm="tokens") or the sum of their weights (norm="weights", meant for w >= 0).  Returns (loss, acc, row_nll)
+    then: row_nll [R] fp32 are the unweighted per-row terms (0 on ignored rows), acc = {sum w l, N}.  weights=None is the path
+    without the option: the same calls with the same arguments, and the (loss, acc) pair.
     Domain: targets in [0, V) or equal to ignore_index; anything else is undefined on the fused path."""
-    loss, acc = LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled(), float(label_smoothing))
-    return loss, acc
+    if weights is None:
+        if norm not in K.LOSS_NORMS:
+            raise ValueError(f"lm_head_ce: norm={norm!r} is not one of {sorted(K.LOSS_NORMS)}")
+        loss, acc = LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled(), float(label_smoothing))
+        return loss, acc
+    K.check_loss_weights("lm_head_ce", weights, h.numel() // h.shape[-1], rows_per_weight, h.device, norm)
+    return LmHeadCeFn.apply(h, anchor, emb16_pad, egrad, targets, V, ignore_index, torch.is_grad_enabled(), float(label_smoothing),
+                            weights.detach(), rows_per_weight, norm)
 
 
 class ColamFn(Function):

@@ -42,6 +42,7 @@ class TrainArgs:
     grad_stats_every: int = 0             # --grad_stats_every N: per-parameter gradient / weight statistics every N steps (FusedAdamW)
     grad_accum_steps: int = 1             # --grad_accum_steps K: K batches per optimizer step (FusedAdamW(accum_steps=K)); one process
     deterministic: bool = False           # --deterministic True: the step runs in ops.set_deterministic mode (bitwise reproducible run to run)
+    loss_norm: str = "tokens"             # --loss_norm: divisor of a weighted text loss (batch["loss_weights"]): the non-pad tokens, or "weights" = their weight sum
 
 
 def param_group_spec(model, args: TrainArgs):
@@ -454,6 +455,9 @@ def forward_losses(model, guide, batch, args: TrainArgs, ready=None, towers=None
         names_mask, _ = K.prep_ids(batch["names_art_ids"], cfg.pad_token_id)                 # TRAIN:270
         kw = dict(face_features=batch["face_emb"], face_mask=K.face_mask(batch["face_emb"]), name_ids=batch["names_art_ids"],
                   name_mask=names_mask)
+    if batch.get("loss_weights") is not None:
+        # optional batch key: fp32 [B] (per caption) or [B, T] (per token) weights of the text loss; SECLA and CoLaM do not see them
+        kw = dict(kw, loss_weights=batch["loss_weights"], loss_norm=args.loss_norm)
     out = model(input_ids=src, attention_mask=src_mask, decoder_input_ids=tgt_in, image_features=img_cls, labels=tgt,
                 output_logits=False, add_ner_ffn=True, output_attentions=False, **kw)         # TRAIN:281 + fused CE (TRAIN:287); the step uses no maps
     txt = out["loss"]
@@ -699,6 +703,172 @@ def gen_caption_from_loader_bart(model, batches, beam_size, max_length, device="
     return out_dict
 
 
+# ---- self-critical sequence training (Rennie et al. 2017): loss = sum_c A_c NLL(sample_c) / tokens over captions the model sampled,
+# A_c = reward_c - baseline of its group.  The weighted fused LM head (batch key / model(loss_weights=)) is the loss; everything
+# here is host-side glue around generate(do_sample=True) and one teacher-forced pass.
+def sequences_to_labels(seqs, pad, eos, T=None):
+    """[R, L] id rows of generate(do_sample=True) — start token, tokens, eos, then pad — as (decoder_input_ids, labels), both [R, T]
+    (T=None: L - 1; the caller passes max_length - 1 so the shape is the same at every step; L > T + 1 is a ValueError).
+    labels[r] = seqs[r, 1:] up to and including the FIRST eos behind the start token (the start token may itself be the eos id),
+    pad after it and up to T; a row without eos keeps every token.  A pad id that occurs before the eos stays where it is: it does
+    not end the caption, and as the loss's ignore index that one position carries no loss.  decoder_input_ids = start token, then
+    labels[:, :-1] (shift right).  Runs where `seqs` lives, host or device."""
+    if seqs.dim() != 2 or seqs.shape[1] < 2:
+        raise ValueError(f"sequences_to_labels: seqs must be [rows, L >= 2], got {tuple(seqs.shape)}")
+    R, L = seqs.shape
+    T = L - 1 if T is None else int(T)
+    if L > T + 1:
+        raise ValueError(f"sequences_to_labels: rows of {L} ids do not fit T + 1 = {T + 1} (T = max_length - 1)")
+    labels = seqs.new_full((R, T), pad)
+    labels[:, :L - 1] = seqs[:, 1:]
+    is_eos = labels == eos
+    behind = (is_eos.cumsum(1) - is_eos.to(torch.int64)) > 0          # strictly behind the first eos
+    labels = torch.where(behind, torch.full_like(labels, pad), labels)
+    dec_in = torch.cat([seqs[:, :1], labels[:, :-1]], 1)
+    return dec_in.contiguous(), labels.contiguous()
+
+
+def group_advantages(rewards, n, baseline="mean"):
+    """fp32 [len(rewards)] advantages: every run of n consecutive rewards (the n samples of one image, generate()'s row order) minus
+    the run's mean ("mean"; sums to 0 per run) or minus the mean of the run's other n - 1 rewards ("leave_one_out").  n = 1 would
+    make every advantage 0 (or divide by zero): ValueError."""
+    if baseline not in ("mean", "leave_one_out"):
+        raise ValueError(f"group_advantages: baseline={baseline!r} is not 'mean' or 'leave_one_out'")
+    if not isinstance(n, int) or n < 2:
+        raise ValueError(f"group_advantages: n={n!r} samples per group: a baseline needs at least 2")
+    r = torch.as_tensor(rewards, dtype=torch.float64).reshape(-1)
+    if r.numel() % n != 0:
+        raise ValueError(f"group_advantages: {r.numel()} rewards are not groups of n={n}")
+    g = r.view(-1, n)
+    s = g.sum(1, keepdim=True)
+    base = s / n if baseline == "mean" else (s - g) / (n - 1)
+    return (g - base).reshape(-1).to(torch.float32)
+
+
+def overlap_f1_reward(samples, refs, special_ids=()):
+    """clipped unigram F1 of token ids, one float per (sample, reference) pair: overlap = sum over ids of min(count in sample, count
+    in reference), precision = overlap / len(sample), recall = overlap / len(reference), ids in `special_ids` (pad, eos, start)
+    dropped from both first; an empty sample or reference, or no overlap, scores 0.  A stand-in that needs no tokenizer and no
+    metric package (caption metrics are outside SURVEY §8): any callable (samples, refs) -> list[float] takes its place."""
+    from collections import Counter
+    if len(samples) != len(refs):
+        raise ValueError(f"overlap_f1_reward: {len(samples)} samples but {len(refs)} references")
+    special = set(int(i) for i in special_ids)
+    out = []
+    for s, r in zip(samples, refs):
+        cs, cr = Counter(int(t) for t in s if int(t) not in special), Counter(int(t) for t in r if int(t) not in special)
+        ns, nr = sum(cs.values()), sum(cr.values())
+        ov = sum(min(c, cr[t]) for t, c in cs.items())
+        if ns == 0 or nr == 0 or ov == 0:
+            out.append(0.0)
+            continue
+        p, q = ov / ns, ov / nr
+        out.append(2.0 * p * q / (p + q))
+    return out
+
+
+def check_scst_flags(scst_samples, grad_accum_steps=1, world_size=1):
+    """the trainers' up-front refusals for --scst_samples N > 0: the self-critical step is one process, one batch per update."""
+    if scst_samples < 0 or scst_samples == 1:
+        raise ValueError(f"--scst_samples {scst_samples}: 0 (off) or at least 2 samples per image (the baseline is their mean)")
+    if scst_samples and grad_accum_steps > 1:
+        raise ValueError(f"--scst_samples {scst_samples} with --grad_accum_steps {grad_accum_steps}: the self-critical step does not "
+                         "accumulate (DESIGN.md §8)")
+    if scst_samples and world_size > 1:
+        raise ValueError(f"--scst_samples {scst_samples} with world_size {world_size}: the self-critical step is one process (DESIGN.md §8)")
+
+
+def self_critical_step(model, optimizer, batch, args: TrainArgs, reward_fn=overlap_f1_reward, n_samples=4, baseline="mean", ce_weight=0.0,
+                       seed=None, **gen_kw):
+    """One self-critical update: sample n_samples captions per image (generate(do_sample=True, num_return_sequences=n, seed=, **gen_kw)
+    in eval mode, under no_grad), ONE device-to-host copy of the ids, rewards on the host (reward_fn(samples, refs) -> list[float],
+    refs = the batch's caption repeated per sample; the default is overlap_f1_reward without pad / eos / start ids), advantages per
+    group (group_advantages), then one teacher-forced train-mode pass over the B n sampled captions (row b n + j = sample j of image
+    b, the encoder-side inputs repeat_interleave'd n times) with loss_weights = advantages, loss_norm="tokens", the text loss only —
+    no CoLaM (the guide's states belong to the ground-truth caption) and no SECLA (it does not depend on the caption) — backward,
+    optimizer.step with train_step's clip / guard / EMA / statistics, zero_grad.  ce_weight > 0 appends the B ground-truth
+    captions as further rows of weight ce_weight: the same pass, the same weighted loss.
+    Returns a device fp32 vector {loss, mean reward, mean advantage^2, mean log-prob of the sampled tokens under the train-mode
+    pass} without a further sync.  Eager only, one process, one batch per update: a DistributedDataParallel wrapper or an
+    optimizer built with accum_steps > 1 is a ValueError.  max_length (in gen_kw; default generate()'s) fixes T = max_length - 1."""
+    if isinstance(model, DistributedDataParallel):
+        raise ValueError("self_critical_step is one process: pass the bare model, not a DistributedDataParallel wrapper")
+    check_scst_flags(n_samples, max(args.grad_accum_steps, getattr(optimizer, "accum_steps", 1)))
+    if n_samples < 2:
+        raise ValueError(f"self_critical_step: n_samples={n_samples}: at least 2 samples per image (the baseline is their mean)")
+    if ce_weight < 0:
+        raise ValueError(f"self_critical_step: ce_weight={ce_weight} must be >= 0")
+    if args.deterministic and not ops.deterministic():
+        with ops.deterministic_mode(True):
+            return self_critical_step(model, optimizer, batch, args, reward_fn, n_samples, baseline, ce_weight, seed, **gen_kw)
+    if args.skip_nonfinite and not getattr(optimizer, "skip_nonfinite", False):
+        raise ValueError("TrainArgs.skip_nonfinite needs an optimizer built with FusedAdamW(..., skip_nonfinite=True)")
+    if args.ema_decay and getattr(optimizer, "ema_decay", None) is None:
+        raise ValueError("TrainArgs.ema_decay needs an optimizer built with FusedAdamW(..., ema_decay=...)")
+    if args.grad_stats_every and not getattr(optimizer, "grad_stats_every", 0):
+        raise ValueError("TrainArgs.grad_stats_every needs an optimizer built with FusedAdamW(..., grad_stats_every=N)")
+    net, cfg, n = model, model.config, n_samples
+    pad, eos, start = cfg.pad_token_id, cfg.eos_token_id, cfg.decoder_start_token_id
+    max_length = gen_kw.setdefault("max_length", 20)
+    T = max_length - 1
+    tgt = batch["caption_ids"]
+    B, dev = tgt.shape[0], tgt.device
+    # ---- 1. sample, 2. one copy to the host, 3. rewards and advantages there
+    net.eval()
+    try:
+        with torch.no_grad():
+            src, src_mask, feats, kw = _model_inputs(net, batch)
+            seqs = net.generate(input_ids=src, attention_mask=src_mask, image_features=feats, add_ner_ffn=True, do_sample=True,
+                                num_return_sequences=n, seed=seed, **kw, **gen_kw)
+    finally:
+        net.train()
+    seqs_host, refs_host = _ids_to_lists([seqs, tgt])
+    refs = [refs_host[r // n] for r in range(B * n)]
+    if reward_fn is overlap_f1_reward:
+        rewards = overlap_f1_reward(seqs_host, refs, special_ids=(pad, eos, start))
+    else:
+        rewards = reward_fn(seqs_host, refs)
+    adv = group_advantages([float(r) for r in rewards], n, baseline)
+    dec_in, labels = sequences_to_labels(seqs, pad, eos, T)
+    # ---- 4. / 5. rows: B n samples (b n + j), then with ce_weight > 0 the B ground-truth captions
+    weights = adv
+    rep = lambda t: t.repeat_interleave(n, dim=0)                                           # noqa: E731
+    if ce_weight > 0:
+        W = max(T, tgt.shape[1])
+
+        def widen(t):
+            return t if t.shape[1] == W else torch.cat([t, t.new_full((t.shape[0], W - t.shape[1]), pad)], 1)
+        _, gt_in = K.prep_ids(tgt, pad, start_id=eos, want_mask=False)                      # shift_tokens_right as train_step does it
+        dec_in, labels = torch.cat([widen(dec_in), widen(gt_in)]), torch.cat([widen(labels), widen(tgt)])
+        weights = torch.cat([adv, torch.full((B,), float(ce_weight))])
+        rep = lambda t: torch.cat([t.repeat_interleave(n, dim=0), t])                       # noqa: E731
+    host_stats = torch.tensor([sum(rewards) / len(rewards), float((adv.double() ** 2).mean())], dtype=torch.float32)
+    weights, host_stats = weights.to(dev, non_blocking=True), host_stats.to(dev, non_blocking=True)
+    # ---- 6. the train-mode pass with the weighted text loss, 7. backward and the update
+    ops.begin_step()
+    out = net(input_ids=rep(src), attention_mask=rep(src_mask), decoder_input_ids=dec_in.contiguous(), image_features=rep(feats),
+              labels=labels.contiguous(), output_logits=False, add_ner_ffn=True, output_attentions=False, loss_weights=weights.contiguous(),
+              loss_norm="tokens", **{k: rep(v) for k, v in kw.items()})
+    loss = out["loss"]
+    with torch.autograd.set_multithreading_enabled(False):
+        loss.backward(ops.const_one(loss.device))
+    ops.flush_wgrads()
+    streams.join_all()
+    optimizer.step(clip_norm=None if args.no_clip_norm else args.clip_norm)
+    optimizer.zero_grad()
+    nll = out["token_nll"][:B * n]
+    logp = 0.0 - nll.sum() / (labels[:B * n] != pad).sum().clamp(min=1)
+    return torch.cat([loss.detach().view(1), host_stats, logp.view(1)])
+
+
+def _same_loss_weights_key(who, static, batch):
+    """a recorded step holds the launches of the weighted OR of the unweighted text loss: the batch must match what was recorded"""
+    rec, now = static.get("loss_weights") is not None, batch.get("loss_weights") is not None
+    if rec != now:
+        raise ValueError(f"{who}: recorded {'with' if rec else 'without'} batch['loss_weights'], called {'with' if now else 'without'} "
+                         "it (the weighted text loss is a different launch sequence: record a step of its own)")
+
+
 class GraphedTrainStep:
     """The whole training step (all streams: compute, guide, weight gradients) captured once into a hipGraph and
     replayed per batch — "HIP graphs instead of a tracing compiler".  A step is ~2400 kernel launches that eager Python
@@ -726,6 +896,7 @@ class GraphedTrainStep:
             self.out4 = train_step(model, guide, optimizer, self.static, args)
 
     def __call__(self, batch):
+        _same_loss_weights_key("GraphedTrainStep", self.static, batch)
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         self.graph.replay()
@@ -824,6 +995,7 @@ class PlannedTrainStep:
         from . import _lib
         if K._stream() != self.stream:
             raise RuntimeError("PlannedTrainStep: replay on the stream the plan was recorded on")
+        _same_loss_weights_key("PlannedTrainStep", self.static, batch)
         self._before(batch, ready)
         if ready is not None:
             torch.cuda.current_stream().wait_event(ready)
