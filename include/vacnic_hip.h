@@ -614,12 +614,49 @@ int vacnic_bias_grad(const void* dy, float* dbias, int64_t M, int64_t N, int64_t
 int vacnic_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream);
 
 /* ---- decode (transformers 4.18 GenerationMixin.beam_search driven at TRAIN:513-520, DDPINF:758-842) ---- */
+/*
+ * Bad-word table (transformers 4.18 NoBadWordsLogitsProcessor), device memory, shared by vacnic_beam_init / vacnic_beam_step and
+ * vacnic_sample_step: bad_words int32 [n_bad][VACNIC_BAD_WORD_LEN], word w in its row's first bad_len[w] entries (the rest -1),
+ * bad_len int32 [n_bad], 1 <= bad_len[w] <= VACNIC_BAD_WORD_LEN.  n_bad = 0 (NULL tables) = off; n_bad > VACNIC_BAD_WORDS_MAX is
+ * refused with VACNIC_UNSUPPORTED.  With a row's history h[0 .. cur_len - 1] (its decoder input so far, INCLUDING the start token), a
+ * word of m tokens bans its last token w[m - 1] for the next position iff m - 1 <= cur_len and h[cur_len - (m - 1) + k] == w[k] for
+ * every 0 <= k < m - 1 (4.18's _tokens_match): a one-token word is banned at every position, and a prefix as long as the WHOLE
+ * history matches.  A banned token scores -inf; it joins the NoRepeatNGram bans and the MinLength suppression in one set, and a
+ * forced position overrides all of them.  Ids outside [0, V) and lengths outside [1, VACNIC_BAD_WORD_LEN] in the table are skipped.
+ */
+#define VACNIC_BAD_WORDS_MAX 1024
+#define VACNIC_BAD_WORD_LEN 16
 /* Per beam row: log_softmax(logits[:V]) -> NoRepeatNGram bans (bans int32 [R][n_ban], -1 = none) -> MinLength
  * (suppress_eos) -> ForcedEOS (forced_token >= 0: that token scores 0, all others -inf) -> + beam_scores[r] ->
  * top-K (sorted, ties broken towards the lower token id).  top_val f32 [R][K], top_idx int32 [R][K]. */
 int vacnic_beam_topk(const void* logits, const float* beam_scores, const int32_t* bans, int32_t n_ban, int32_t eos,
                      int32_t suppress_eos, int32_t forced_token, float* top_val, int32_t* top_idx, int64_t R, int64_t V,
                      int64_t ldl, int32_t K, int32_t logits_f32, void* stream);
+/*
+ * vacnic_beam_topk with the repetition penalty (transformers 4.18 RepetitionPenaltyLogitsProcessor).  The first fields are the
+ * arguments of vacnic_beam_topk; with penalty_rule == 0 the call IS vacnic_beam_topk.  Otherwise history int32 [R][hist_stride]
+ * holds row r's decoder input so far in its first cur_len entries, INCLUDING the start token (for BART the eos id: eos is penalised
+ * from position 1, as in HF), 1 <= cur_len <= min(hist_stride, 1024), and P = penalty is a finite number > 0 (P < 1 rewards
+ * repetition).  pen(x) = x < 0 ? x * P : x / P is ONE IEEE-754 fp32 operation, applied to every DISTINCT history token j in
+ * [0, V) once, however often j occurs:
+ *   penalty_rule 1, on the logits (HF greedy_search / sample run the processors on raw logits; generate() uses it for one beam):
+ *     z'_j = pen(z_j) before anything else; the log-softmax, the bans, the beam score and the top-K all see z'.
+ *   penalty_rule 2, on the scores (HF beam_search runs the processors on log_softmax(logits); generate() uses it for > 1 beam):
+ *     s_j = z_j - lse(z) with the log-sum-exp of the UNPENALISED row (history tokens included), s'_j = pen(s_j); then the bans,
+ *     then + beam_scores[r] (each of the three a separately rounded fp32 operation), then the top-K.
+ * A banned or suppressed token scores -inf whatever its penalty; a forced position ignores the penalty.  Order of the result as in
+ * vacnic_beam_topk (score desc, token asc) — under rule 2 over the final scores, and entries behind the last finite score read
+ * (-inf, -1) there, whichever kernel serves the shape (a forced position reads as in vacnic_beam_topk).  -inf stays -inf.
+ * VACNIC_BAD_SHAPE: as vacnic_beam_topk; penalty_rule outside 0 .. 2; with a rule: history NULL, P not a finite number > 0, cur_len
+ * outside [1, hist_stride].  VACNIC_UNSUPPORTED: cur_len > 1024 with a rule.
+ */
+typedef struct {
+  const void* logits; const float* beam_scores; const int32_t* bans; float* top_val; int32_t* top_idx; const int32_t* history;
+  int64_t R, V, ldl, hist_stride;
+  int32_t n_ban, eos, suppress_eos, forced_token, K, logits_f32, cur_len, penalty_rule;
+  float penalty;
+} vacnic_beam_topk_args;
+int vacnic_beam_topk_ex(const vacnic_beam_topk_args* a, void* stream);
 /*
  * LM head + vacnic_beam_topk of the single-token decoder fused (MFULL:1997 `lm_head(outputs[0]) + final_logits_bias`, then the
  * log_softmax -> processors -> + beam_scores -> topk of beam_search above): R <= 8 rows, d_model <= 1024.  The [R][V] logits never
@@ -632,12 +669,18 @@ int vacnic_beam_topk(const void* logits, const float* beam_scores, const int32_t
  *   of 8 up to 1024, V <= 65536, K2 <= min(64, V), and the merge's G x K2 candidates (8 bytes each, G = workgroups of the part kernel,
  *   449 at V = 50265) fit the 160 KiB of LDS: K2 <= 45 at V = 50265.  Callers choose between this call and the GEMM -> vacnic_beam_topk
  *   chain with it.
+ *   history / hist_stride / cur_len / penalty_rule / penalty: the repetition penalty exactly as in vacnic_beam_topk_ex (0 / NULL =
+ *   off; the optional logits output stays unpenalised).  penalty_rule 2 needs R * hist_stride more floats of workspace behind the
+ *   vacnic_lmhead_topk_workspace(R, V, K2) ones.  A penalty changes neither the shapes the call accepts nor
+ *   vacnic_lmhead_topk_supported.
  */
 typedef struct {
   const void* h; const void* emb; const float* bias; float* logits; float* workspace;
   const float* beam_scores; const int32_t* bans; float* top_val; int32_t* top_idx;
   int64_t R, V, d, ldw, ldl, workspace_floats;
   int32_t n_ban, eos, suppress_eos, forced_token, K2;
+  int32_t cur_len, penalty_rule; float penalty;
+  const int32_t* history; int64_t hist_stride;
 } vacnic_lmhead_topk_args;
 int64_t vacnic_lmhead_topk_workspace(int64_t R, int64_t V, int32_t K2);
 int32_t vacnic_lmhead_topk_supported(int64_t R, int64_t V, int64_t d, int32_t K2);
@@ -652,14 +695,20 @@ int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream);
  * vacnic_beam_init: histories = [start], beam scores = [0, -1e9, ...], empty lists.
  * vacnic_beam_step(cur_len): consumes beam_topk's [R][K2] candidates of the position whose histories hold cur_len tokens
  * (seq[(cur_len-1)&1]) and writes seq[cur_len&1], beam_scores (the next beam_topk's input), next_ids (last tokens, int64 [R]),
- * src_idx (int64 [R]: the row each new beam continues = KV-cache reorder index) and bans (int32 [R][Lmax], -1 padded; NULL if
- * no_repeat_ngram_size == 0).
+ * src_idx (int64 [R]: the row each new beam continues = KV-cache reorder index) and bans (int32 [R][Lmax + n_bad], -1 padded; NULL
+ * if no_repeat_ngram_size == 0 and n_bad == 0).
+ * bad_words / bad_len / n_bad (the table above; 0 / NULL = off): the bad-word bans of the NEXT position are appended to each row's
+ * ban list behind the NoRepeatNGram bans (the same token may appear twice; the order inside a list is unspecified), one-token words
+ * included, so the top-k kernels need nothing but `bans` with n_ban = Lmax + n_bad.  vacnic_beam_init writes the first position's
+ * (history = [start]).  As with the n-gram bans, the rows of a finished batch item ban nothing.  n_bad > 0 with bans == NULL:
+ * VACNIC_BAD_SHAPE.
  */
 typedef struct {
   int32_t* seq[2]; float* beam_scores; int32_t* done; int32_t* hyp_cnt; double* hyp_worst; double* hyp_score; int32_t* hyp_len;
   int32_t* hyp_seq; int64_t* next_ids; int64_t* src_idx; int32_t* bans;
   int64_t B, nb, Lmax, V, eos, pad, no_repeat_ngram_size, early_stopping;
   float length_penalty;
+  const int32_t* bad_words; const int32_t* bad_len; int64_t n_bad;
 } vacnic_beam_state;
 int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token, void* stream);
 int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len,
@@ -671,16 +720,22 @@ int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const in
  *
  * Inputs.  logits fp32 [R][ldl], the first V columns are real.  seq int32 [R][Lmax]: row r's history, cur_len tokens long
  * (1 <= cur_len < Lmax).  done int32 [R].  params: 8 32-bit words of DEVICE memory, read at run time so that a captured launch
- * serves every setting: [0] temperature T (f32)  [1] top_k (i32)  [2] top_p (f32)  [3] reserved  [4],[5] seed (low, high word)
- * [6],[7] call counter (low, high word).  A T that is not > 0 is read as 1.
+ * serves every setting: [0] temperature T (f32)  [1] top_k (i32)  [2] top_p (f32)  [3] repetition penalty P (f32)  [4],[5] seed
+ * (low, high word)  [6],[7] call counter (low, high word).  A T that is not > 0 is read as 1; a P that is not > 0 (the 0 of a
+ * block written without one) is read as 1 = off.  bad_words / bad_len / n_bad: the bad-word table above (0 / NULL = off).
  *
  * Per row r, in this order:
  * 1. Processors.  done[r] != 0: the row writes `pad` (log-prob 0) and nothing else happens to it.  forced_token >= 0: that token is
  *    chosen with probability 1 (log-prob 0, kept = 1, thr = 0, mass = 1).  Otherwise token j becomes -inf if suppress_eos != 0 and
  *    j == eos (MinLength), or, with n = no_repeat_ngram_size > 0 and cur_len + 1 >= n, if j == seq[r][i + n - 1] for some
  *    0 <= i <= cur_len - n with seq[r][i .. i + n - 2] == seq[r][cur_len - n + 1 .. cur_len - 1] (NoRepeatNGram, computed from the
- *    history in place).  A NaN logit counts as -inf, +inf as FLT_MAX.  A row without a finite logit left emits `eos`
- *    (log-prob 0, kept = 0) and finishes.
+ *    history in place), or if the bad-word table bans it for this history (the rule above, also computed in place).  Before the
+ *    bans, with P != 1 (RepetitionPenaltyLogitsProcessor on the raw logits, as HF's sample runs it): every DISTINCT token j of the
+ *    history seq[r][0 .. cur_len - 1] (start token included, so BART's eos is penalised from position 1) has its logit replaced by
+ *    z_j < 0 ? z_j * P : z_j / P — ONE IEEE-754 fp32 multiplication or division, applied once however often j occurs; for these
+ *    tokens NaN is read as -inf and +inf as FLT_MAX first; -inf stays -inf.  P < 1 rewards repetition.  Everything below (steps 2-6,
+ *    the reported log-prob included) sees the penalised logits.  A NaN logit counts as -inf, +inf as FLT_MAX.  A row without a
+ *    finite logit left emits `eos` (log-prob 0, kept = 0) and finishes.
  * 2. Temperature.  z' = z / T: ONE IEEE-754 fp32 division, round to nearest even (not a multiplication by a reciprocal);
  *    -0 is read as +0.
  * 3. Top-k.  With 1 <= top_k < V: thr_k = the top_k-th largest z' counting duplicates and -inf entries; every z' >= thr_k stays,
@@ -703,14 +758,15 @@ int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const in
  *    nothing was cut); mass[r] = Z / Zl (1 when top-p is off); u[r] = fp32(u), round to nearest even (written for every row).
  *    u itself lies in (0, 1), but 2 m + 1 needs 25 bits once m >= 2^23 and fp32 holds 24: there the copy is rounded, and for
  *    m = 2^24 - 1 it reads exactly 1.0.  Only this diagnostic is rounded: the draw compares the integers above.
- * VACNIC_UNSUPPORTED: V outside [1, 65536].  VACNIC_BAD_SHAPE: a null operand, R < 1, ldl < V, cur_len outside [1, Lmax),
- * forced_token >= V, a negative n-gram size.
+ * VACNIC_UNSUPPORTED: V outside [1, 65536], n_bad outside [0, VACNIC_BAD_WORDS_MAX].  VACNIC_BAD_SHAPE: a null operand (a table
+ * pointer with n_bad > 0 included), R < 1, ldl < V, cur_len outside [1, Lmax), forced_token >= V, a negative n-gram size.
  */
 typedef struct {
   const float* logits; const void* params; int32_t* seq; int32_t* done; int64_t* next_ids; float* logp;
   int32_t* kept; float* thr; float* mass; float* u;
   int64_t R, V, ldl, Lmax;
   int32_t cur_len, eos, pad, no_repeat_ngram_size, suppress_eos, forced_token;
+  const int32_t* bad_words; const int32_t* bad_len; int32_t n_bad;
 } vacnic_sample_step_args;
 int vacnic_sample_step(const vacnic_sample_step_args* a, void* stream);
 /*

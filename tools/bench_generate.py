@@ -2,9 +2,11 @@
 run_full_train.sh:10), beam 5, max_length 50, length_penalty 2.0, seed 42; synthetic GoodNews-shaped inputs.
 
     bench_generate.py [n] [batch] [--num_beams N] [--do_sample [--top_k K] [--top_p P] [--temperature T] [--num_return_sequences N]]
+                      [--repetition_penalty P] [--bad_words 3,4;50264]
 
 --do_sample times sampling decode at the same shape (one beam; rows = batch x num_return_sequences); --num_beams 1 is the greedy
-decode it goes beside.
+decode it goes beside.  --repetition_penalty / --bad_words (comma-separated ids, `;` between words) switch the two logits
+processors on; without them the calls are the ones of before.
 
     bench_generate.py --kernel [--rows 1,8] [--vocab 50265]
 
@@ -85,6 +87,8 @@ def main():
     ap.add_argument("--top_p", type=float, default=1.0)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--num_return_sequences", type=int, default=1)
+    ap.add_argument("--repetition_penalty", type=float, default=1.0)
+    ap.add_argument("--bad_words", default="")
     a = ap.parse_args()
     if a.kernel:
         return kernel_mode([int(r) for r in a.rows.split(",")], a.vocab)
@@ -96,6 +100,12 @@ def main():
     else:
         mode = dict(num_beams=a.num_beams, length_penalty=2.0)
         what = f"beam {a.num_beams}"
+    if a.repetition_penalty != 1.0:
+        mode["repetition_penalty"] = a.repetition_penalty
+        what += f", repetition_penalty {a.repetition_penalty}"
+    if a.bad_words:
+        mode["bad_words_ids"] = [[int(t) for t in w.split(",")] for w in a.bad_words.split(";")]
+        what += f", {len(mode['bad_words_ids'])} bad words"
     cfg, vcfg = bart_large_vit_l14()
     model, _, clip_model = build_models(cfg, vcfg, device="cuda", seed=42, init="device")
     model.eval()

@@ -137,18 +137,26 @@ BeamState = _struct("vacnic_beam_state", [
     ("seq0", vp), ("seq1", vp), ("beam_scores", vp), ("done", vp), ("hyp_cnt", vp), ("hyp_worst", vp), ("hyp_score", vp), ("hyp_len", vp),
     ("hyp_seq", vp), ("next_ids", vp), ("src_idx", vp), ("bans", vp),
     ("B", i64), ("nb", i64), ("Lmax", i64), ("V", i64), ("eos", i64), ("pad", i64), ("no_repeat_ngram_size", i64), ("early_stopping", i64),
-    ("length_penalty", f32)])
+    ("length_penalty", f32), ("bad_words", vp), ("bad_len", vp), ("n_bad", i64)])
 
 LmheadTopkArgs = _struct("vacnic_lmhead_topk_args", [
     ("h", vp), ("emb", vp), ("bias", vp), ("logits", vp), ("workspace", vp), ("beam_scores", vp), ("bans", vp), ("top_val", vp), ("top_idx", vp),
     ("R", i64), ("V", i64), ("d", i64), ("ldw", i64), ("ldl", i64), ("workspace_floats", i64),
-    ("n_ban", i32), ("eos", i32), ("suppress_eos", i32), ("forced_token", i32), ("K2", i32)])
+    ("n_ban", i32), ("eos", i32), ("suppress_eos", i32), ("forced_token", i32), ("K2", i32),
+    ("cur_len", i32), ("penalty_rule", i32), ("penalty", f32), ("history", vp), ("hist_stride", i64)])
+
+BeamTopkArgs = _struct("vacnic_beam_topk_args", [
+    ("logits", vp), ("beam_scores", vp), ("bans", vp), ("top_val", vp), ("top_idx", vp), ("history", vp),
+    ("R", i64), ("V", i64), ("ldl", i64), ("hist_stride", i64),
+    ("n_ban", i32), ("eos", i32), ("suppress_eos", i32), ("forced_token", i32), ("K", i32), ("logits_f32", i32), ("cur_len", i32),
+    ("penalty_rule", i32), ("penalty", f32)])
 
 SampleStepArgs = _struct("vacnic_sample_step_args", [
     ("logits", vp), ("params", vp), ("seq", vp), ("done", vp), ("next_ids", vp), ("logp", vp),
     ("kept", vp), ("thr", vp), ("mass", vp), ("u", vp),
     ("R", i64), ("V", i64), ("ldl", i64), ("Lmax", i64),
-    ("cur_len", i32), ("eos", i32), ("pad", i32), ("no_repeat_ngram_size", i32), ("suppress_eos", i32), ("forced_token", i32)])
+    ("cur_len", i32), ("eos", i32), ("pad", i32), ("no_repeat_ngram_size", i32), ("suppress_eos", i32), ("forced_token", i32),
+    ("bad_words", vp), ("bad_len", vp), ("n_bad", i32)])
 
 DecoderLayer = _struct("vacnic_decoder_layer", [
     ("w_kvq", vp), ("w_so", vp), ("w_cq", vp), ("w_co", vp), ("w_fc1", vp), ("w_fc2", vp),
@@ -209,6 +217,7 @@ _STRUCT_FNS = {
     "vacnic_grad_guard": GradGuardArgs, "vacnic_param_stats": ParamStatsArgs, "vacnic_lmhead_ce_fwd": LmheadCeArgs,
     "vacnic_lmhead_eval": LmheadEvalArgs,
     "vacnic_decoder_step": DecoderStepArgs, "vacnic_lmhead_topk": LmheadTopkArgs, "vacnic_sample_step": SampleStepArgs,
+    "vacnic_beam_topk_ex": BeamTopkArgs,
 }
 _PLAIN_FNS = {
     "vacnic_combine_losses": [vp, vp, vp, vp, f32, f32, vp, vp],

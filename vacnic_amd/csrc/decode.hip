@@ -12,22 +12,42 @@ __device__ __forceinline__ float ldl(const void* row, int j) {
   return F32 ? ((const float*)row)[j] : bf2f(((const bf16_t*)row)[j]);
 }
 
+// RepetitionPenaltyLogitsProcessor (include/vacnic_hip.h at vacnic_beam_topk_ex): x < 0 ? x * p : x / p, one IEEE operation.
+// RULE 1 applies it to the raw logits of the history tokens (before the log-softmax), RULE 2 to their log-softmax scores.
+struct PenP { const int32_t* hist; long hstride; int cur_len; float pen; };
+__device__ __forceinline__ float penalise(float x, float pen) { return x < 0.f ? __fmul_rn(x, pen) : __fdiv_rn(x, pen); }
+constexpr int PEN_HIST_MAX = 1024;      // history tokens a penalised call may hold (cur_len)
+
 // one block per row; K rounds of block-wide arg-max under the strict order (score desc, index asc)
-template <bool F32>
+template <bool F32, int RULE>
 __global__ __launch_bounds__(256) void beam_topk_kernel(const void* __restrict__ logits, const float* __restrict__ beam_scores,
                                                         const int* __restrict__ bans, int n_ban, int eos, int suppress_eos,
                                                         int forced_token, float* __restrict__ top_val, int* __restrict__ top_idx,
-                                                        int V, long ldl_, int K) {
+                                                        int V, long ldl_, int K, PenP pp) {
   __shared__ float rv[256];
   __shared__ int ri[256];
   __shared__ float s_lse;
+  __shared__ int sh_hist[RULE ? PEN_HIST_MAX : 1];
   const long r = blockIdx.x;
   const char* row = (const char*)logits + r * ldl_ * (F32 ? 4 : 2);
   const int* ban = bans ? bans + r * n_ban : nullptr;
-  // ---- log-sum-exp of the raw logits
+  if (RULE) {
+    for (int i = threadIdx.x; i < pp.cur_len; i += 256) sh_hist[i] = pp.hist[r * pp.hstride + i];
+    __syncthreads();
+  }
+  auto in_hist = [&](int j) -> bool {
+    bool hit = false;
+    for (int i = 0; i < pp.cur_len; ++i) hit = hit || sh_hist[i] == j;
+    return hit;
+  };
+  auto zl = [&](int j) -> float {                          // the logit the log-softmax sees
+    const float v = ldl<F32>(row, j);
+    return (RULE == 1 && forced_token < 0 && in_hist(j)) ? penalise(v, pp.pen) : v;
+  };
+  // ---- log-sum-exp of the raw logits (RULE 1: of the penalised logits)
   float m = -INFINITY, s = 0.f;
   for (int j = threadIdx.x; j < V; j += 256) {
-    const float v = ldl<F32>(row, j);
+    const float v = zl(j);
     const float nm = fmaxf(m, v);
     s = s * __expf(m - nm) + __expf(v - nm);
     m = nm;
@@ -48,7 +68,11 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const void* __restrict__
     if (forced_token >= 0) return j == forced_token ? base : -INFINITY;       // ForcedEOSTokenLogitsProcessor
     if (suppress_eos && j == eos) return -INFINITY;                            // MinLengthLogitsProcessor
     for (int b = 0; b < n_ban; ++b) if (ban && ban[b] == j) return -INFINITY;  // NoRepeatNGramLogitsProcessor
-    return ldl<F32>(row, j) - lse + base;
+    if (RULE == 2) {
+      const float sj = ldl<F32>(row, j) - lse;
+      return __fadd_rn(in_hist(j) ? penalise(sj, pp.pen) : sj, base);
+    }
+    return zl(j) - lse + base;
   };
   float last_v = INFINITY; int last_i = -1;
   for (int k = 0; k < K; ++k) {
@@ -68,7 +92,9 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const void* __restrict__
       __syncthreads();
     }
     last_v = rv[0]; last_i = ri[0];
-    if (threadIdx.x == 0) { top_val[r * K + k] = last_v; top_idx[r * K + k] = last_i == 0x7fffffff ? -1 : last_i; }
+    // (rule 2, as in the threshold variant: a score of -inf is no candidate, the entries behind the finite ones read (-inf, -1))
+    const bool none = last_i == 0x7fffffff || (RULE == 2 && forced_token < 0 && last_v == -INFINITY);
+    if (threadIdx.x == 0) { top_val[r * K + k] = last_v; top_idx[r * K + k] = none ? -1 : last_i; }
     __syncthreads();
   }
 }
@@ -123,11 +149,17 @@ __device__ __forceinline__ void block_argmax(float& bv, int& bi, float* rv, int*
   }
 }
 
-template <bool F32>
+// RULE 1 (penalty on the logits): the walk hands out penalised logits, nothing else changes.  RULE 2 (penalty on the scores): a
+// penalised token's rank depends on the log-sum-exp, which is known only after pass 1 — so the DISTINCT history tokens are kept out
+// of the threshold / pick passes (they count as banned there, but stay in the log-sum-exp), the K picks of the other tokens go to
+// LDS instead of HBM, the history tokens (<= cur_len) are scored once lse is known, and a rank merge under the strict order
+// (score desc, token asc) writes the best K of both lists.  Scores of -inf are not candidates then: the entries behind the finite
+// ones read (-inf, -1).
+template <bool F32, int RULE>
 __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void* __restrict__ logits, const float* __restrict__ beam_scores,
                                                                       const int* __restrict__ bans, int n_ban, int eos, int suppress_eos,
                                                                       float* __restrict__ top_val, int* __restrict__ top_idx,
-                                                                      int V, long ldl_, int K) {
+                                                                      int V, long ldl_, int K, PenP pp) {
   extern __shared__ unsigned banbits[];               // ceil(V/32) words, then scratch
   const int nwords = (V + 31) >> 5;
   float* rv = (float*)(banbits + nwords);             // [16]
@@ -135,12 +167,19 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void
   float* tm = (float*)(ri + 16);                      // [1024] thread maxima
   float* cand_v = tm + TOPK_THREADS;                  // [TOPK_CAND]
   int* cand_i = (int*)(cand_v + TOPK_CAND);           // [TOPK_CAND]
-  int* cnt = cand_i + TOPK_CAND;                      // [1]
+  int* cnt = cand_i + TOPK_CAND;                      // [1] (+ [1]: history tokens, [2]: valid entries of the merge)
+  unsigned* histbits = (unsigned*)(cnt + 4);          // RULE > 0: [nwords]
+  float* pick_v = (float*)(histbits + nwords);        // RULE 2: [TOPK_THREADS] the picks of the other tokens, final scores
+  int* pick_i = (int*)(pick_v + TOPK_THREADS);        //         [TOPK_THREADS]
+  float* hist_v = (float*)(pick_i + TOPK_THREADS);    //         [PEN_HIST_MAX] the distinct, unbanned history tokens: final scores
+  int* hist_i = (int*)(hist_v + PEN_HIST_MAX);        //         [PEN_HIST_MAX]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long r = blockIdx.x;
   const char* row = (const char*)logits + r * ldl_ * (F32 ? 4 : 2);
   for (int w = tid; w < nwords; w += TOPK_THREADS) banbits[w] = 0u;
-  if (tid == 0) *cnt = 0;
+  if (RULE)
+    for (int w = tid; w < nwords; w += TOPK_THREADS) histbits[w] = 0u;
+  if (tid < 3) cnt[tid] = 0;
   __syncthreads();
   if (bans) {
     for (int b = tid; b < n_ban; b += TOPK_THREADS) {
@@ -149,12 +188,43 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void
     }
   }
   if (suppress_eos && tid == 0 && eos >= 0 && eos < V) atomicOr(&banbits[eos >> 5], 1u << (eos & 31));
+  if (RULE) {
+    for (int i = tid; i < pp.cur_len; i += TOPK_THREADS) {
+      const int t = pp.hist[r * pp.hstride + i];
+      if (t >= 0 && t < V) atomicOr(&histbits[t >> 5], 1u << (t & 31));
+    }
+  }
   __syncthreads();
+  if (RULE == 2) {
+    // the distinct history tokens that no processor bans -> the list; then all of them count as banned in the passes below
+    for (int w = tid; w < nwords; w += TOPK_THREADS) {
+      unsigned hb = histbits[w];
+      unsigned live = hb & ~banbits[w];
+      while (live) {
+        const int bit = __ffs((int)live) - 1;
+        live &= live - 1u;
+        hist_i[atomicAdd(&cnt[1], 1)] = (w << 5) + bit;        // <= cur_len <= PEN_HIST_MAX entries
+      }
+      banbits[w] |= hb;
+    }
+    __syncthreads();
+  }
   const bool vec = F32 && ((uintptr_t)row & 15) == 0;
   const int nvec = vec ? (V >> 2) : 0;
   auto masked = [&](int j, float v) -> float { return (banbits[j >> 5] >> (j & 31)) & 1u ? -INFINITY : v; };
-  // generic row walk: f(j, raw logit) over this thread's share, 16-byte loads four deep where the layout allows
-  auto walk = [&](auto&& f) {
+  auto pz = [&](int j, float v) -> float {
+    return (RULE == 1 && ((histbits[j >> 5] >> (j & 31)) & 1u)) ? penalise(v, pp.pen) : v;
+  };
+  // one pick: to HBM, or (RULE 2) to LDS for the merge with the history tokens
+  auto emit = [&](int k, float bv, int bi, float lse_, float base_) {
+    const float fv = bv == -INFINITY ? -INFINITY : bv - lse_ + base_;
+    const int fi = bi == 0x7fffffff ? -1 : bi;
+    if (RULE == 2) { pick_v[k] = fv; pick_i[k] = fi; }
+    else { top_val[r * K + k] = fv; top_idx[r * K + k] = fi; }
+  };
+  // generic row walk: f(j, logit) over this thread's share, 16-byte loads four deep where the layout allows
+  auto walk = [&](auto&& f0) {
+    auto f = [&](int j, float v) { f0(j, pz(j, v)); };
     for (int v0 = tid; v0 < nvec; v0 += 4 * TOPK_THREADS) {
       f32x4 x[4];
 #pragma unroll
@@ -195,6 +265,10 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void
 #pragma unroll
   for (int w = 0; w < TOPK_THREADS / 64; ++w) tot += rv[w];
   const float lse = gm + logf(tot), base = beam_scores ? beam_scores[r] : 0.f;
+  if (RULE == 2) {
+    for (int i = tid; i < cnt[1]; i += TOPK_THREADS)
+      hist_v[i] = __fadd_rn(penalise(ldl<F32>(row, hist_i[i]) - lse, pp.pen), base);
+  }
   // ---- threshold: a lower bound of the K-th best score from K distinct elements
   float T = -INFINITY;
   if (K <= TOPK_THREADS / 64) {
@@ -257,15 +331,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void
           for (int u = 0; u < 4; ++u)
             if (ci[u] == bi) { cv[u] = -INFINITY; ci[u] = 0x7fffffff; }
         }
-        if (lane == 0) {
-          top_val[r * K + k] = bv == -INFINITY ? -INFINITY : bv - lse + base;
-          top_idx[r * K + k] = bi == 0x7fffffff ? -1 : bi;
-        }
+        if (lane == 0) emit(k, bv, bi, lse, base);
       }
     }
-    return;
-  }
-  if (!overflow) {
+    if (RULE != 2) return;
+  } else if (!overflow) {
     const int n = *cnt;
     float cv = tid < n ? cand_v[tid] : -INFINITY;
     int ci = tid < n ? cand_i[tid] : 0x7fffffff;
@@ -273,28 +343,47 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_fast_kernel(const void
       float bv = cv; int bi = ci;
       block_argmax(bv, bi, rv, ri, lane, wave);
       if (bi == ci && ci != 0x7fffffff) { cv = -INFINITY; ci = 0x7fffffff; }
-      if (tid == 0) {
-        top_val[r * K + k] = bv == -INFINITY ? -INFINITY : bv - lse + base;
-        top_idx[r * K + k] = bi == 0x7fffffff ? -1 : bi;
-      }
+      if (tid == 0) emit(k, bv, bi, lse, base);
     }
-    return;
+    if (RULE != 2) return;
+  } else {
+    // ---- fallback: K arg-max passes over the row (massive ties / fewer than K finite scores)
+    float last_v = INFINITY; int last_i = -1;
+    for (int k = 0; k < K; ++k) {
+      float bv = -INFINITY; int bi = 0x7fffffff;
+      walk([&](int j, float v) {
+        const float sv = masked(j, v);
+        const bool after = (sv < last_v) || (sv == last_v && j > last_i);
+        if (after && (sv > bv || (sv == bv && j < bi))) { bv = sv; bi = j; }
+      });
+      block_argmax(bv, bi, rv, ri, lane, wave);
+      last_v = bv; last_i = bi;
+      if (tid == 0) emit(k, bv, bi, lse, base);
+    }
   }
-  // ---- fallback: K arg-max passes over the row (massive ties / fewer than K finite scores)
-  float last_v = INFINITY; int last_i = -1;
-  for (int k = 0; k < K; ++k) {
-    float bv = -INFINITY; int bi = 0x7fffffff;
-    walk([&](int j, float v) {
-      const float sv = masked(j, v);
-      const bool after = (sv < last_v) || (sv == last_v && j > last_i);
-      if (after && (sv > bv || (sv == bv && j < bi))) { bv = sv; bi = j; }
-    });
-    block_argmax(bv, bi, rv, ri, lane, wave);
-    last_v = bv; last_i = bi;
-    if (tid == 0) {
-      top_val[r * K + k] = bv == -INFINITY ? -INFINITY : bv - lse + base;
-      top_idx[r * K + k] = bi == 0x7fffffff ? -1 : bi;
+  if (RULE == 2) {
+    // ---- rank merge of the K picks and the history tokens: an entry's slot is the number of entries that precede it under the strict
+    // order (score desc, token asc; the token ids are distinct).  Scores of -inf do not take part.
+    __syncthreads();
+    const int nh = cnt[1], ne = K + nh;
+    auto ent = [&](int e, float& v, int& i) {
+      if (e < K) { v = pick_v[e]; i = pick_i[e]; } else { v = hist_v[e - K]; i = hist_i[e - K]; }
+    };
+    for (int e = tid; e < ne; e += TOPK_THREADS) {
+      float v; int i;
+      ent(e, v, i);
+      if (i < 0 || !(v > -INFINITY)) continue;
+      int rank = 0;
+      for (int o = 0; o < ne; ++o) {
+        float ov; int oi;
+        ent(o, ov, oi);
+        if (oi >= 0 && ov > -INFINITY && (ov > v || (ov == v && oi < i))) ++rank;
+      }
+      atomicAdd(&cnt[2], 1);
+      if (rank < K) { top_val[r * K + rank] = v; top_idx[r * K + rank] = i; }
     }
+    __syncthreads();
+    for (int k = cnt[2] + tid; k < K; k += TOPK_THREADS) { top_val[r * K + k] = -INFINITY; top_idx[r * K + k] = -1; }
   }
 }
 
@@ -322,12 +411,19 @@ struct LmTopkP {
   const bf16_t* h; const bf16_t* emb; const float* bias; float* logits; float* part;
   const int* bans; const float* beam_scores; float* top_val; int* top_idx;
   int R, V, K, ldw, ldl, n_ban, eos, suppress_eos, forced, K2, G, tpw;      // tpw: 16-column tiles per workgroup
+  // repetition penalty (rule 0 = off): histories int32 [R][hstride], cur_len tokens each; rule 2: side f32 [R][hstride] in the workspace
+  const int32_t* hist; float* side; int hstride, cur_len, rule; float pen;
 };
 
-template <int KS>                     // K steps (32 wide) per wave: K <= 128 * KS
+// Repetition penalty.  RULE 1 (on the logits): a history token's logit is penalised before it enters the (max, sum-exp) pieces and the
+// row buffer; the logits output stays raw.  RULE 2 (on the scores): the history tokens stay in the (max, sum-exp) pieces but are kept
+// out of the workgroup's candidate list; their masked logits go to side[r][i] (i = every history position that holds the token) and
+// the merge kernel scores them once the log-sum-exp is known.
+template <int KS, int RULE>           // K steps (32 wide) per wave: K <= 128 * KS
 __global__ __launch_bounds__(256) void lmhead_part_kernel(LmTopkP p) {
   __shared__ float sc[8][LT_MAXCOLS];                               // masked logits of this workgroup's columns
   __shared__ unsigned banw[8][LT_MAXCOLS / 32];
+  __shared__ unsigned histw[RULE ? 8 : 1][LT_MAXCOLS / 32];
   __shared__ __attribute__((aligned(16))) float red[2][4][256];     // the 4 waves' partial tiles, double-buffered by tile parity
   __shared__ float rm[64], rs[64];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -367,6 +463,14 @@ __global__ __launch_bounds__(256) void lmhead_part_kernel(LmTopkP p) {
     }
   }
   if (p.suppress_eos && tid < p.R && p.eos >= c_lo && p.eos < c_lo + ncol) atomicOr(&banw[tid][(p.eos - c_lo) >> 5], 1u << ((p.eos - c_lo) & 31));
+  if (RULE) {
+    for (int i = tid; i < 8 * (LT_MAXCOLS / 32); i += 256) (&histw[0][0])[i] = 0u;
+    __syncthreads();
+    for (int i = tid; i < p.R * p.cur_len; i += 256) {
+      const int t = p.hist[(size_t)(i / p.cur_len) * p.hstride + i % p.cur_len] - c_lo;
+      if (t >= 0 && t < ncol) atomicOr(&histw[i / p.cur_len][t >> 5], 1u << (t & 31));
+    }
+  }
   __syncthreads();
   float mrun = -INFINITY, srun = 0.f;                               // wave 0, lanes with col < R: row `col`, columns q * 4 .. + 3 of every tile
   const bool fin = wave == 0 && col < p.R;
@@ -393,12 +497,13 @@ __global__ __launch_bounds__(256) void lmhead_part_kernel(LmTopkP p) {
       for (int v = 0; v < 4; ++v) {
         const int n = t * 16 + q * 4 + v;
         if (n < p.V) {
-          const float x = ((s0[v] + s1[v]) + s2[v]) + s3[v] + bv[v];
+          float x = ((s0[v] + s1[v]) + s2[v]) + s3[v] + bv[v];
           if (p.logits) p.logits[(size_t)col * p.ldl + n] = x;
+          const int j = n - c_lo;
+          if (RULE == 1 && ((histw[col][j >> 5] >> (j & 31)) & 1u)) x = penalise(x, p.pen);
           const float nm = fmaxf(mrun, x);
           srun = srun * __expf(mrun - nm) + __expf(x - nm);
           mrun = nm;
-          const int j = n - c_lo;
           sc[col][j] = (banw[col][j >> 5] >> (j & 31)) & 1u ? -INFINITY : x;
         }
       }
@@ -410,6 +515,13 @@ __global__ __launch_bounds__(256) void lmhead_part_kernel(LmTopkP p) {
   }
   if (wave == 0) { rm[lane] = mrun; rs[lane] = srun; }
   __syncthreads();
+  if (RULE == 2) {
+    for (int i = tid; i < p.R * p.cur_len; i += 256) {
+      const int r = i / p.cur_len, pos = i % p.cur_len;
+      const int t = p.hist[(size_t)r * p.hstride + pos] - c_lo;
+      if (t >= 0 && t < ncol) p.side[(size_t)r * p.hstride + pos] = sc[r][t];
+    }
+  }
   const int W = 2 + 2 * p.K2;
   for (int r = wave; r < p.R; r += 4) {
     float* out = p.part + (size_t)r * W * p.G + blockIdx.x;         // field f at out[f * G]
@@ -423,8 +535,9 @@ __global__ __launch_bounds__(256) void lmhead_part_kernel(LmTopkP p) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int j = lane + 64 * u;
-      cv[u] = j < ncol ? sc[r][j] : -INFINITY;
-      ci[u] = j < ncol ? c_lo + j : 0x7fffffff;
+      const bool in = j < ncol && !(RULE == 2 && ((histw[r][j >> 5] >> (j & 31)) & 1u));
+      cv[u] = in ? sc[r][j] : -INFINITY;
+      ci[u] = in ? c_lo + j : 0x7fffffff;
     }
     for (int k = 0; k < p.K2; ++k) {
       float bv = cv[0]; int bi = ci[0];
@@ -509,6 +622,7 @@ __global__ __launch_bounds__(256) void lmhead_merge_kernel(LmTopkP p) {
   // its (<= 2) lists in registers, a round is one workgroup-wide arg-best over them and the winner steps to its list's next entry.
   // (Scanning all G x K2 candidates per round — 18 dependent LDS round trips per thread — cost 40 us.)
   float hv[2]; int hi[2], hp[2];
+  float my_v = -INFINITY; int my_i = -1;            // rule 2: thread k keeps pick k
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int g = tid + 256 * u;
@@ -528,7 +642,9 @@ __global__ __launch_bounds__(256) void lmhead_merge_kernel(LmTopkP p) {
 #pragma unroll
     for (int w = 1; w < 4; ++w)
       if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
-    if (tid == 0) {
+    if (p.rule == 2) {
+      if (tid == k && bi != 0x7fffffff) { my_v = bv - lse + base; my_i = bi; }
+    } else if (tid == 0) {
       const bool none = bi == 0x7fffffff;
       p.top_val[(size_t)r * K2 + k] = none ? -INFINITY : bv - lse + base;
       p.top_idx[(size_t)r * K2 + k] = none ? -1 : bi;
@@ -544,6 +660,43 @@ __global__ __launch_bounds__(256) void lmhead_merge_kernel(LmTopkP p) {
         }
     }
   }
+  if (p.rule != 2) return;
+  // ---- rule 2: the history tokens, scored now that lse is known, merged with the K2 picks by rank under the strict order (score
+  // desc, token asc; token ids are distinct).  The candidate lists are dead: the picks move into their LDS.  side[r][i] turns from
+  // the masked logit of history position i into its final score, -inf for a repeated position (the first one speaks for the token).
+  __syncthreads();
+  float* pick_v = (float*)lt_smem;                 // [K2]
+  int* pick_i = (int*)(pick_v + K2);               // [K2]
+  if (tid < K2) { pick_v[tid] = my_v; pick_i[tid] = my_i; }
+  if (tid == 0) ri[0] = 0;
+  const int32_t* h = p.hist + (size_t)r * p.hstride;
+  float* sd = p.side + (size_t)r * p.hstride;
+  const int nh = p.cur_len;
+  for (int i = tid; i < nh; i += 256) {
+    const int t = h[i];
+    bool first = t >= 0 && t < p.V;
+    for (int o = 0; o < i; ++o) first = first && h[o] != t;
+    sd[i] = first ? __fadd_rn(penalise(sd[i] - lse, p.pen), base) : -INFINITY;
+  }
+  __syncthreads();                                  // (the workgroup's own global stores are visible to it behind the barrier)
+  for (int e = tid; e < K2 + nh; e += 256) {
+    const float v = e < K2 ? pick_v[e] : sd[e - K2];
+    const int i = e < K2 ? pick_i[e] : h[e - K2];
+    if (i < 0 || !(v > -INFINITY)) continue;
+    int rank = 0;
+    for (int o = 0; o < K2; ++o) {
+      const float ov = pick_v[o]; const int oi = pick_i[o];
+      if (oi >= 0 && (ov > v || (ov == v && oi < i))) ++rank;
+    }
+    for (int o = 0; o < nh; ++o) {
+      const float ov = sd[o];
+      if (ov > -INFINITY && (ov > v || (ov == v && h[o] < i))) ++rank;
+    }
+    atomicAdd(&ri[0], 1);
+    if (rank < K2) { p.top_val[(size_t)r * K2 + rank] = v; p.top_idx[(size_t)r * K2 + rank] = i; }
+  }
+  __syncthreads();
+  for (int k = ri[0] + tid; k < K2; k += 256) { p.top_val[(size_t)r * K2 + k] = -INFINITY; p.top_idx[(size_t)r * K2 + k] = -1; }
 }
 
 // dst[r][:row_bytes] = src[g][:row_bytes], g = idx[r] (period == 0) or (r / period) * period + idx[r % period] (the same beam
@@ -569,13 +722,14 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const char* __restrict
 //   done              int32 [B];  hyp_cnt int32 [B];  hyp_worst f64 [B]
 //   hyp_score f64 [B][nb], hyp_len int32 [B][nb], hyp_seq int32 [B][nb][Lmax]      finished hypotheses, in list order
 // Outputs for the next position: next_ids int64 [R] (last tokens), src_idx int64 [R] (beam each new row continues: the
-// KV-cache reorder index), bans int32 [R][Lmax] (-1 padded).
+// KV-cache reorder index), bans int32 [R][Lmax + n_bad] (-1 padded): the NoRepeatNGram bans, then the bad-word bans (NoBadWords).
 struct BeamP {
   const float* top_val; const int32_t* top_idx;      // [R][K2] from beam_topk (scores include the beam score)
   const int32_t* seq_in; int32_t* seq_out;
   float* beam_scores; int32_t* done; int32_t* hyp_cnt; double* hyp_worst; double* hyp_score; int32_t* hyp_len; int32_t* hyp_seq;
   int64_t* next_ids; int64_t* src_idx; int32_t* bans;
-  int nb, K2, Lmax, cur_len, V, eos, pad, ngram, early;
+  const int32_t* bad_words; const int32_t* bad_len;
+  int nb, K2, Lmax, cur_len, V, eos, pad, ngram, early, n_bad;
   double lenpow;      // cur_len ^ length_penalty from the HOST's pow: the device's is an ulp off for some lengths (19 ^ 2.0), which moved
                       // hyp_score off the value transformers computes
 };
@@ -727,7 +881,8 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(BeamP p) {
       // (a wave's LDS operations execute in order: the history written above is visible to all its lanes here)
       const int n = p.ngram, len = cur + 1;               // histories now hold cur + 1 tokens
       const int* sq = sseq[j];
-      int32_t* bn = p.bans + (size_t)row * L;
+      const int nbw = L + p.n_bad;                         // row length of the ban lists: <= len - n + 1 n-gram bans, <= n_bad bad words
+      int32_t* bn = p.bans + (size_t)row * nbw;
       if (n > 0 && len + 1 >= n && !is_done) {
         for (int i = lane; i <= len - n; i += 64) {
           bool match = true;
@@ -735,51 +890,112 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(BeamP p) {
           if (match) bn[atomicAdd(&nban[j], 1)] = sq[i + n - 1];
         }
       }
+      if (!is_done) {
+        // NoBadWords of the next position: word w of m tokens bans w[m - 1] if the last m - 1 tokens of the history are w[0 .. m - 2]
+        for (int w = lane; w < p.n_bad; w += 64) {
+          const int m = p.bad_len[w];
+          if (m < 1 || m > VACNIC_BAD_WORD_LEN || m - 1 > len) continue;
+          const int32_t* bw = p.bad_words + (size_t)w * VACNIC_BAD_WORD_LEN;
+          bool match = true;
+          for (int k = 0; k < m - 1; ++k) match = match && bw[k] == sq[len - (m - 1) + k];
+          const int t = bw[m - 1];
+          if (match && t >= 0 && t < p.V) bn[atomicAdd(&nban[j], 1)] = t;
+        }
+      }
       const int nb_ = nban[j];
-      for (int i = nb_ + lane; i < L; i += 64) bn[i] = -1;
+      for (int i = nb_ + lane; i < nbw; i += 64) bn[i] = -1;
     }
   }
 }
 
 __global__ void beam_init_kernel(int32_t* seq, float* beam_scores, int32_t* done, int32_t* hyp_cnt, double* hyp_worst, int64_t* next_ids,
-                                 int32_t* bans, int R, int nb, int L, int start, int pad) {
+                                 int32_t* bans, int R, int nb, int L, int start, int pad, int n_bad) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < R * L) {
-    seq[i] = (i % L) == 0 ? start : pad;
-    if (bans) bans[i] = -1;
-  }
+  if (i < R * L) seq[i] = (i % L) == 0 ? start : pad;
+  if (i < R * (L + n_bad) && bans) bans[i] = -1;
   if (i < R) { beam_scores[i] = (i % nb) == 0 ? 0.f : -1e9f; next_ids[i] = start; }
   if (i < R / nb) { done[i] = 0; hyp_cnt[i] = 0; hyp_worst[i] = 1e9; }
 }
+
+// NoBadWords of the FIRST position (history = [start]): the one-token words, and the two-token words that begin with the start token.
+// One workgroup per row, launched behind beam_init_kernel (which filled the lists with -1) only when there is a table.
+__global__ __launch_bounds__(256) void beam_init_bad_words_kernel(int32_t* bans, const int32_t* bad_words, const int32_t* bad_len, int n_bad,
+                                                                  int nbw, int V, int start) {
+  __shared__ int cnt;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  int32_t* bn = bans + (size_t)blockIdx.x * nbw;
+  for (int w = threadIdx.x; w < n_bad; w += 256) {
+    const int m = bad_len[w];
+    const int32_t* bw = bad_words + (size_t)w * VACNIC_BAD_WORD_LEN;
+    if (m == 1 || (m == 2 && bw[0] == start)) {
+      const int t = bw[m - 1];
+      if (t >= 0 && t < V) bn[atomicAdd(&cnt, 1)] = t;
+    }
+  }
+}
 }  // namespace
+
+template <int RULE>
+static void beam_topk_launch(const vacnic_beam_topk_args* a, hipStream_t s) {
+  const PenP pp = {a->history, (long)a->hist_stride, RULE ? (int)a->cur_len : 0, a->penalty};
+  const int V = (int)a->V, K = a->K;
+  // (a penalised call keeps two bitmaps of the vocabulary and the merge lists in LDS: the fast kernel up to V = 65536)
+  if (a->forced_token < 0 && K <= TOPK_THREADS && a->V <= (RULE ? 65536 : 262144)) {
+    size_t lds = ((size_t)((V + 31) >> 5) + 32 + TOPK_THREADS + 2 * TOPK_CAND + 4) * 4;
+    if (RULE) lds += (size_t)((V + 31) >> 5) * 4;
+    if (RULE == 2) lds += (size_t)(2 * TOPK_THREADS + 2 * PEN_HIST_MAX) * 4;
+    if (a->logits_f32)
+      hipLaunchKernelGGL((beam_topk_fast_kernel<true, RULE>), dim3((unsigned)a->R), dim3(TOPK_THREADS), lds, s, a->logits, a->beam_scores, a->bans,
+                         a->n_ban, a->eos, a->suppress_eos, a->top_val, a->top_idx, V, (long)a->ldl, K, pp);
+    else
+      hipLaunchKernelGGL((beam_topk_fast_kernel<false, RULE>), dim3((unsigned)a->R), dim3(TOPK_THREADS), lds, s, a->logits, a->beam_scores, a->bans,
+                         a->n_ban, a->eos, a->suppress_eos, a->top_val, a->top_idx, V, (long)a->ldl, K, pp);
+    return;
+  }
+  if (a->logits_f32)
+    hipLaunchKernelGGL((beam_topk_kernel<true, RULE>), dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->beam_scores, a->bans, a->n_ban, a->eos,
+                       a->suppress_eos, a->forced_token, a->top_val, a->top_idx, V, (long)a->ldl, K, pp);
+  else
+    hipLaunchKernelGGL((beam_topk_kernel<false, RULE>), dim3((unsigned)a->R), dim3(256), 0, s, a->logits, a->beam_scores, a->bans, a->n_ban, a->eos,
+                       a->suppress_eos, a->forced_token, a->top_val, a->top_idx, V, (long)a->ldl, K, pp);
+}
+
+static int beam_topk_checked(const vacnic_beam_topk_args* a, void* stream) {
+  VCHECK(a->logits && a->top_val && a->top_idx, VACNIC_BAD_SHAPE, "beam_topk: null operand");
+  VCHECK(a->V > 0 && a->ldl >= a->V && a->K > 0 && a->K <= a->V, VACNIC_BAD_SHAPE, "beam_topk: bad V/ldl/K");
+  VCHECK(a->penalty_rule >= 0 && a->penalty_rule <= 2, VACNIC_BAD_SHAPE, "beam_topk: penalty_rule %d outside 0 .. 2", (int)a->penalty_rule);
+  if (a->penalty_rule != 0) {
+    VCHECK(a->history, VACNIC_BAD_SHAPE, "beam_topk: a penalty needs the histories (null operand)");
+    VCHECK(a->penalty > 0.f && a->penalty <= 3.4028234e38f, VACNIC_BAD_SHAPE, "beam_topk: the penalty must be a finite number > 0");
+    VCHECK(a->cur_len >= 1 && a->cur_len <= a->hist_stride, VACNIC_BAD_SHAPE, "beam_topk: cur_len %d outside [1, hist_stride=%ld]", (int)a->cur_len,
+           (long)a->hist_stride);
+    VCHECK(a->cur_len <= PEN_HIST_MAX, VACNIC_UNSUPPORTED, "beam_topk: a penalty over %d history tokens, at most %d", (int)a->cur_len, PEN_HIST_MAX);
+  }
+  if (a->R == 0) return VACNIC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->penalty_rule == 1) beam_topk_launch<1>(a, s);
+  else if (a->penalty_rule == 2) beam_topk_launch<2>(a, s);
+  else beam_topk_launch<0>(a, s);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
 
 extern "C" int vacnic_beam_topk(const void* logits, const float* beam_scores, const int32_t* bans, int32_t n_ban, int32_t eos,
                                 int32_t suppress_eos, int32_t forced_token, float* top_val, int32_t* top_idx, int64_t R, int64_t V,
                                 int64_t ldl, int32_t K, int32_t logits_f32, void* stream) {
   VPLAN_REC(vacnic_beam_topk, logits, beam_scores, bans, n_ban, eos, suppress_eos, forced_token, top_val, top_idx, R, V, ldl, K, logits_f32, stream);
-  VCHECK(logits && top_val && top_idx, VACNIC_BAD_SHAPE, "beam_topk: null operand");
-  VCHECK(V > 0 && ldl >= V && K > 0 && K <= V, VACNIC_BAD_SHAPE, "beam_topk: bad V/ldl/K");
-  if (R == 0) return VACNIC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (forced_token < 0 && K <= TOPK_THREADS && V <= 262144) {
-    const size_t lds = ((size_t)((V + 31) >> 5) + 32 + TOPK_THREADS + 2 * TOPK_CAND + 4) * 4;
-    if (logits_f32)
-      hipLaunchKernelGGL(beam_topk_fast_kernel<true>, dim3((unsigned)R), dim3(TOPK_THREADS), lds, s, logits, beam_scores, bans, n_ban,
-                         eos, suppress_eos, top_val, top_idx, (int)V, (long)ldl, K);
-    else
-      hipLaunchKernelGGL(beam_topk_fast_kernel<false>, dim3((unsigned)R), dim3(TOPK_THREADS), lds, s, logits, beam_scores, bans, n_ban,
-                         eos, suppress_eos, top_val, top_idx, (int)V, (long)ldl, K);
-    VLAUNCH_CHECK();
-    return VACNIC_OK;
-  }
-  if (logits_f32)
-    hipLaunchKernelGGL(beam_topk_kernel<true>, dim3((unsigned)R), dim3(256), 0, s, logits, beam_scores, bans, n_ban, eos,
-                       suppress_eos, forced_token, top_val, top_idx, (int)V, (long)ldl, K);
-  else
-    hipLaunchKernelGGL(beam_topk_kernel<false>, dim3((unsigned)R), dim3(256), 0, s, logits, beam_scores, bans, n_ban, eos,
-                       suppress_eos, forced_token, top_val, top_idx, (int)V, (long)ldl, K);
-  VLAUNCH_CHECK();
-  return VACNIC_OK;
+  vacnic_beam_topk_args a = {};
+  a.logits = logits; a.beam_scores = beam_scores; a.bans = bans; a.top_val = top_val; a.top_idx = top_idx;
+  a.R = R; a.V = V; a.ldl = ldl; a.n_ban = n_ban; a.eos = eos; a.suppress_eos = suppress_eos; a.forced_token = forced_token; a.K = K;
+  a.logits_f32 = logits_f32;
+  return beam_topk_checked(&a, stream);
+}
+
+extern "C" int vacnic_beam_topk_ex(const vacnic_beam_topk_args* a, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_beam_topk_ex, a, stream);
+  VCHECK(a, VACNIC_BAD_SHAPE, "beam_topk: null operand");
+  return beam_topk_checked(a, stream);
 }
 
 static int lt_tiles_per_wg(int64_t V) {
@@ -824,6 +1040,16 @@ extern "C" int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream
   p.eos = a->eos; p.suppress_eos = a->suppress_eos; p.forced = a->forced_token; p.K2 = a->K2;
   p.tpw = lt_tiles_per_wg(a->V);
   p.G = (int)(((a->V + 15) / 16 + p.tpw - 1) / p.tpw);
+  p.hist = nullptr; p.side = nullptr; p.hstride = 0; p.cur_len = 0; p.rule = 0; p.pen = 1.f;
+  VCHECK(a->penalty_rule >= 0 && a->penalty_rule <= 2, VACNIC_BAD_SHAPE, "lmhead_topk: penalty_rule %d outside 0 .. 2", (int)a->penalty_rule);
+  if (a->penalty_rule != 0 && a->forced_token < 0) {
+    VCHECK(a->history, VACNIC_BAD_SHAPE, "lmhead_topk: a penalty needs the histories (null operand)");
+    VCHECK(a->penalty > 0.f && a->penalty <= 3.4028234e38f, VACNIC_BAD_SHAPE, "lmhead_topk: the penalty must be a finite number > 0");
+    VCHECK(a->cur_len >= 1 && a->cur_len <= a->hist_stride && a->hist_stride <= 0x7fffffffLL, VACNIC_BAD_SHAPE,
+           "lmhead_topk: cur_len %d outside [1, hist_stride=%ld]", (int)a->cur_len, (long)a->hist_stride);
+    VCHECK(a->cur_len <= PEN_HIST_MAX, VACNIC_UNSUPPORTED, "lmhead_topk: a penalty over %d history tokens, at most %d", (int)a->cur_len, PEN_HIST_MAX);
+    p.hist = a->history; p.hstride = (int)a->hist_stride; p.cur_len = a->cur_len; p.rule = a->penalty_rule; p.pen = a->penalty;
+  }
   hipStream_t s = (hipStream_t)stream;
   if (a->forced_token >= 0) {
     VCHECK(a->forced_token < a->V, VACNIC_BAD_SHAPE, "lmhead_topk: forced token outside the vocabulary");
@@ -837,8 +1063,9 @@ extern "C" int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream
          "lmhead_topk: d_model <= 1024, a multiple of 8, 16-byte aligned rows");
   VCHECK(p.tpw * 16 <= LT_MAXCOLS, VACNIC_UNSUPPORTED, "lmhead_topk: vocabulary above %d columns", 512 * LT_MAXCOLS);
   VCHECK(!a->logits || a->ldl >= a->V, VACNIC_BAD_SHAPE, "lmhead_topk: ldl < V");
-  VCHECK(a->workspace_floats >= vacnic_lmhead_topk_workspace(a->R, a->V, a->K2), VACNIC_BAD_SHAPE, "lmhead_topk: workspace of %ld floats, need %ld",
-         (long)a->workspace_floats, (long)vacnic_lmhead_topk_workspace(a->R, a->V, a->K2));
+  const int64_t ws_need = vacnic_lmhead_topk_workspace(a->R, a->V, a->K2) + (p.rule == 2 ? a->R * a->hist_stride : 0);
+  VCHECK(a->workspace_floats >= ws_need, VACNIC_BAD_SHAPE, "lmhead_topk: workspace of %ld floats, need %ld", (long)a->workspace_floats, (long)ws_need);
+  if (p.rule == 2) p.side = a->workspace + vacnic_lmhead_topk_workspace(a->R, a->V, a->K2);
   const size_t lds_merge = lt_merge_lds(a->V, a->K2);
   VCHECK(lds_merge + LT_MERGE_STATIC <= LT_LDS_MAX, VACNIC_UNSUPPORTED, "lmhead_topk: %d workgroups x K2=%d candidates need %ld bytes of LDS in the merge, above %ld",
          p.G, (int)a->K2, (long)(lds_merge + LT_MERGE_STATIC), (long)LT_LDS_MAX);
@@ -850,8 +1077,16 @@ extern "C" int vacnic_lmhead_topk(const vacnic_lmhead_topk_args* a, void* stream
     }
     lds_raised = true;
   }
-  if (a->d > 256) hipLaunchKernelGGL(lmhead_part_kernel<8>, dim3((unsigned)p.G), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(lmhead_part_kernel<2>, dim3((unsigned)p.G), dim3(256), 0, s, p);
+  if (p.rule == 1) {
+    if (a->d > 256) hipLaunchKernelGGL((lmhead_part_kernel<8, 1>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((lmhead_part_kernel<2, 1>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+  } else if (p.rule == 2) {
+    if (a->d > 256) hipLaunchKernelGGL((lmhead_part_kernel<8, 2>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((lmhead_part_kernel<2, 2>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+  } else {
+    if (a->d > 256) hipLaunchKernelGGL((lmhead_part_kernel<8, 0>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((lmhead_part_kernel<2, 0>), dim3((unsigned)p.G), dim3(256), 0, s, p);
+  }
   VLAUNCH_CHECK();
   hipLaunchKernelGGL(lmhead_merge_kernel, dim3((unsigned)a->R), dim3(256), lds_merge, s, p);
   VLAUNCH_CHECK();
@@ -881,11 +1116,21 @@ extern "C" int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token
   VPLAN_REC_STRUCT(vacnic_beam_init, st, start_token, stream);
   VCHECK(st && st->seq[0] && st->beam_scores && st->done && st->hyp_cnt && st->hyp_worst && st->next_ids, VACNIC_BAD_SHAPE, "beam_init: null state");
   VCHECK(st->B > 0 && st->nb > 0 && st->Lmax > 0, VACNIC_BAD_SHAPE, "beam_init: bad sizes");
+  VCHECK(st->n_bad >= 0 && st->n_bad <= VACNIC_BAD_WORDS_MAX, VACNIC_UNSUPPORTED, "beam_init: %ld bad words, at most %d", (long)st->n_bad,
+         (int)VACNIC_BAD_WORDS_MAX);
+  VCHECK(st->n_bad == 0 || (st->bad_words && st->bad_len && st->bans), VACNIC_BAD_SHAPE, "beam_init: bad words need their table and a ban buffer (null operand)");
   const int R = (int)(st->B * st->nb);
-  const int n = R * (int)st->Lmax;
+  const int nbw = (int)(st->Lmax + st->n_bad);
+  const int n = R * nbw;
   hipLaunchKernelGGL(beam_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st->seq[0], st->beam_scores,
-                     st->done, st->hyp_cnt, st->hyp_worst, st->next_ids, st->bans, R, (int)st->nb, (int)st->Lmax, start_token, (int)st->pad);
+                     st->done, st->hyp_cnt, st->hyp_worst, st->next_ids, st->bans, R, (int)st->nb, (int)st->Lmax, start_token, (int)st->pad,
+                     (int)st->n_bad);
   VLAUNCH_CHECK();
+  if (st->n_bad > 0) {
+    hipLaunchKernelGGL(beam_init_bad_words_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, st->bans, st->bad_words, st->bad_len,
+                       (int)st->n_bad, nbw, (int)st->V, start_token);
+    VLAUNCH_CHECK();
+  }
   return VACNIC_OK;
 }
 
@@ -897,12 +1142,16 @@ extern "C" int vacnic_beam_step(const vacnic_beam_state* st, const float* top_va
   VCHECK(st->nb >= 1 && st->nb <= 16 && K2 >= 1 && K2 <= 64 && st->nb * K2 <= 128, VACNIC_UNSUPPORTED, "beam_step: nb <= 16, K2 <= 64, nb*K2 <= 128");
   VCHECK(cur_len >= 1 && cur_len < st->Lmax && st->Lmax <= 512, VACNIC_BAD_SHAPE, "beam_step: cur_len %d outside [1, Lmax=%ld) or Lmax > 512",
          (int)cur_len, (long)st->Lmax);
+  VCHECK(st->n_bad >= 0 && st->n_bad <= VACNIC_BAD_WORDS_MAX, VACNIC_UNSUPPORTED, "beam_step: %ld bad words, at most %d", (long)st->n_bad,
+         (int)VACNIC_BAD_WORDS_MAX);
+  VCHECK(st->n_bad == 0 || (st->bad_words && st->bad_len && st->bans), VACNIC_BAD_SHAPE, "beam_step: bad words need their table and a ban buffer (null operand)");
   BeamP p;
   p.top_val = top_val; p.top_idx = top_idx;
   p.seq_in = st->seq[(cur_len - 1) & 1]; p.seq_out = st->seq[cur_len & 1];
   p.beam_scores = st->beam_scores; p.done = st->done; p.hyp_cnt = st->hyp_cnt; p.hyp_worst = st->hyp_worst; p.hyp_score = st->hyp_score;
   p.hyp_len = st->hyp_len; p.hyp_seq = st->hyp_seq; p.next_ids = st->next_ids; p.src_idx = st->src_idx; p.bans = st->bans;
   p.nb = (int)st->nb; p.K2 = K2; p.Lmax = (int)st->Lmax; p.cur_len = cur_len; p.V = (int)st->V; p.eos = (int)st->eos; p.pad = (int)st->pad;
+  p.bad_words = st->bad_words; p.bad_len = st->bad_len; p.n_bad = (int)st->n_bad;
   p.ngram = (int)st->no_repeat_ngram_size; p.early = (int)st->early_stopping; p.lenpow = pow((double)cur_len, (double)st->length_penalty);
   hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)st->B), dim3((unsigned)(64 * st->nb)), 0, (hipStream_t)stream, p);
   VLAUNCH_CHECK();

@@ -46,12 +46,14 @@ __device__ __forceinline__ u64 wave_sum_u64(u64 v) {
 struct SampleP {
   const float* logits; const uint32_t* params; int32_t* seq; int32_t* done; int64_t* next_ids; float* logp;
   int32_t* kept; float* thr; float* mass; float* u;
+  const int32_t* bad_words; const int32_t* bad_len;
   long ldl;
-  int V, Lmax, cur_len, eos, pad, ngram, suppress_eos, forced;
+  int V, Lmax, cur_len, eos, pad, ngram, suppress_eos, forced, n_bad;
 };
 
 __global__ __launch_bounds__(ST) void sample_step_kernel(SampleP p) {
   __shared__ uint32_t banbits[2048];                      // one bit per token id (V <= 65536)
+  __shared__ uint32_t histbits[2048];                     // tokens of the row's history (repetition penalty)
   __shared__ uint32_t hcnt[SCOPY * SSTRIDE];
   __shared__ u64 hmass[SCOPY * SSTRIDE];
   __shared__ uint32_t bcnt[SBINS];
@@ -68,6 +70,9 @@ __global__ __launch_bounds__(ST) void sample_step_kernel(SampleP p) {
   if (!(T > 0.f)) T = 1.f;
   const int top_k = (int)p.params[1];
   const float top_p = __uint_as_float(p.params[2]);
+  float pen = __uint_as_float(p.params[3]);               // repetition penalty; the 0 of a block written without one reads as 1 = off
+  if (!(pen > 0.f)) pen = 1.f;
+  const bool penal = pen != 1.f;
   const u64 seed = (u64)p.params[4] | ((u64)p.params[5] << 32), call = (u64)p.params[6] | ((u64)p.params[7] << 32);
   const u64 pkey = seed + 0x9E3779B97F4A7C15ull * call;
   uint32_t rnd[4];
@@ -96,17 +101,36 @@ __global__ __launch_bounds__(ST) void sample_step_kernel(SampleP p) {
   }
   // NoRepeatNGram: the tokens that followed an earlier occurrence of the last n - 1 tokens of this row's history
   const int n = p.ngram;
-  const bool bans = n > 0 && p.cur_len + 1 >= n;
-  if (bans) {
-    for (int w = tid; w < 2048; w += ST) banbits[w] = 0u;
+  const bool grams = n > 0 && p.cur_len + 1 >= n;
+  const bool bans = grams || p.n_bad > 0;
+  if (bans || penal) {
+    for (int w = tid; w < 2048; w += ST) { banbits[w] = 0u; histbits[w] = 0u; }
     __syncthreads();
     const int32_t* h = p.seq + (size_t)r * p.Lmax;
     const int len = p.cur_len;
-    for (int i = tid; i <= len - n; i += ST) {
+    if (grams) {
+      for (int i = tid; i <= len - n; i += ST) {
+        bool match = true;
+        for (int k = 0; k < n - 1; ++k) match = match && h[i + k] == h[len - (n - 1) + k];
+        const int t = h[i + n - 1];
+        if (match && t >= 0 && t < V) atomicOr(&banbits[t >> 5], 1u << (t & 31));
+      }
+    }
+    // NoBadWords: word w of m tokens bans w[m - 1] if the last m - 1 history tokens are w[0 .. m - 2] (m - 1 <= cur_len)
+    for (int w = tid; w < p.n_bad; w += ST) {
+      const int m = p.bad_len[w];
+      if (m < 1 || m > VACNIC_BAD_WORD_LEN || m - 1 > len) continue;
+      const int32_t* bw = p.bad_words + (size_t)w * VACNIC_BAD_WORD_LEN;
       bool match = true;
-      for (int k = 0; k < n - 1; ++k) match = match && h[i + k] == h[len - (n - 1) + k];
-      const int t = h[i + n - 1];
+      for (int k = 0; k < m - 1; ++k) match = match && bw[k] == h[len - (m - 1) + k];
+      const int t = bw[m - 1];
       if (match && t >= 0 && t < V) atomicOr(&banbits[t >> 5], 1u << (t & 31));
+    }
+    if (penal) {
+      for (int i = tid; i < len; i += ST) {
+        const int t = h[i];
+        if (t >= 0 && t < V) atomicOr(&histbits[t >> 5], 1u << (t & 31));
+      }
     }
     __syncthreads();
   }
@@ -145,6 +169,18 @@ __global__ __launch_bounds__(ST) void sample_step_kernel(SampleP p) {
   }
   int Vt = wend;
   asm volatile("" : "+s"(Vt));                                              // (keeps 64 load predicates from staying live as masks)
+  if (penal) {
+    // RepetitionPenalty on the raw logits, once per distinct history token — a sweep of its own behind one uniform test, so that
+    // the sweep below is the one of a call without a penalty
+    for_keys([&](int i) {
+      const int j = base + i * 64 + lane;
+      if (j < Vt && ((histbits[j >> 5] >> (j & 31)) & 1u)) {
+        float z = __uint_as_float(key[i]);
+        z = z != z ? -INFINITY : fminf(z, FLT_MAX);
+        key[i] = __float_as_uint(z < 0.f ? __fmul_rn(z, pen) : __fdiv_rn(z, pen));
+      }
+    });
+  }
   for_keys([&](int i) {
     {
       const int j = base + i * 64 + lane;
@@ -315,11 +351,15 @@ extern "C" int vacnic_sample_step(const vacnic_sample_step_args* a, void* stream
          "sample_step: cur_len %d outside [1, Lmax=%ld)", (int)a->cur_len, (long)a->Lmax);
   VCHECK(a->forced_token < a->V && a->no_repeat_ngram_size >= 0, VACNIC_BAD_SHAPE,
          "sample_step: forced token outside the vocabulary, or a negative n-gram size");
+  VCHECK(a->n_bad >= 0 && a->n_bad <= VACNIC_BAD_WORDS_MAX, VACNIC_UNSUPPORTED, "sample_step: %d bad words, at most %d", (int)a->n_bad,
+         (int)VACNIC_BAD_WORDS_MAX);
+  VCHECK(a->n_bad == 0 || (a->bad_words && a->bad_len), VACNIC_BAD_SHAPE, "sample_step: bad-word table missing (null operand)");
   SampleP p;
   p.logits = a->logits; p.params = (const uint32_t*)a->params; p.seq = a->seq; p.done = a->done; p.next_ids = a->next_ids; p.logp = a->logp;
   p.kept = a->kept; p.thr = a->thr; p.mass = a->mass; p.u = a->u;
   p.ldl = (long)a->ldl; p.V = (int)a->V; p.Lmax = (int)a->Lmax; p.cur_len = a->cur_len; p.eos = a->eos; p.pad = a->pad;
   p.ngram = a->no_repeat_ngram_size; p.suppress_eos = a->suppress_eos; p.forced = a->forced_token;
+  p.bad_words = a->bad_words; p.bad_len = a->bad_len; p.n_bad = a->n_bad;
   hipLaunchKernelGGL(sample_step_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, p);
   VLAUNCH_CHECK();
   return VACNIC_OK;

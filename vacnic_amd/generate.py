@@ -13,11 +13,17 @@ What runs where
     `device_beams=False` keeps the host-side scorer (one device->host copy of the [B*beams, 2*beams] candidates per token).
   * sampling (`do_sample=True`, one beam): the same cached decoder, then the fp32 [rows, V] logits and `vacnic_sample_step` —
     processors, temperature, top-k, top-p, one Philox draw, histories / done flags / log-probs — per position (SampleSession).
+  * `repetition_penalty` / `bad_words_ids` (transformers 4.18 RepetitionPenalty / NoBadWords): the bad-word bans of the next position
+    are appended to the ban lists by `vacnic_beam_init` / `vacnic_beam_step` (host loop: `_bad_word_bans`) and matched in place by
+    `vacnic_sample_step`; the penalty is applied by the top-k kernels from the token histories (on the logits for one beam and for
+    sampling, on the log-softmax scores for more beams).  Off (1.0 / None) the calls are the ones of before.
 
 The cache is preallocated ([layers, B*beams, max_length, 2d] bf16, k|v interleaved per row) instead of the reference's
 per-step torch.cat (MFULL:489-492).
 """
+import numbers
 import os
+import struct
 
 import torch
 
@@ -112,6 +118,52 @@ def _banned(seq, n):
         return []
     prefix = tuple(seq[len(seq) - (n - 1):]) if n > 1 else ()
     return [seq[i + n - 1] for i in range(len(seq) - n + 1) if tuple(seq[i:i + n - 1]) == prefix]
+
+
+def _bad_word_bans(seq, words):
+    """NoBadWordsLogitsProcessor of transformers 4.18 for one history: the last token of every word whose other tokens end the
+    history (a one-token word always; a prefix as long as the whole history matches)."""
+    out = []
+    for w in words:
+        m = len(w)
+        if m - 1 <= len(seq) and (m == 1 or tuple(seq[len(seq) - (m - 1):]) == tuple(w[:-1])):
+            out.append(w[-1])
+    return out
+
+
+def _f32(x):
+    """x rounded to float32, as the kernels receive it (inf where it overflows)"""
+    try:
+        return struct.unpack("<f", struct.pack("<f", float(x)))[0]
+    except OverflowError:
+        return float("inf") if x > 0 else float("-inf")
+
+
+def _check_processor_args(model, repetition_penalty, bad_words_ids):
+    """the checks of RepetitionPenaltyLogitsProcessor / NoBadWordsLogitsProcessor (transformers 4.18) plus this library's capacity;
+    returns the bad words as a tuple of tuples without [eos] and without duplicates, or None"""
+    p = repetition_penalty
+    # the kernels take the penalty as fp32: it has to be finite and > 0 after that rounding (1e39 would be inf, 1e-50 would be 0)
+    ok = isinstance(p, numbers.Real) and not isinstance(p, bool)
+    if ok:
+        ok = 0.0 < _f32(p) < float("inf")
+    if not ok:
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive, finite float (as float32), but is {p!r}")
+    if bad_words_ids is None:
+        return None
+    if not isinstance(bad_words_ids, (list, tuple)) or len(bad_words_ids) == 0:
+        raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids!r}.")
+    if any(not isinstance(w, (list, tuple)) or len(w) == 0 for w in bad_words_ids):
+        raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists, but is {bad_words_ids!r}.")
+    V = int(model.V) if getattr(model, "V", None) is not None else int(model.config.vocab_size)
+    if any(isinstance(t, bool) or not isinstance(t, int) or t < 0 or t >= V for w in bad_words_ids for t in w):
+        raise ValueError(f"Each list in `bad_words_ids` has to be a list of integers in [0, {V}), but is {bad_words_ids!r}.")
+    eos = model.config.eos_token_id
+    words = tuple(dict.fromkeys(tuple(w) for w in bad_words_ids if tuple(w) != (eos,)))       # [eos] is dropped, as 4.18 drops it
+    if len(words) > K.BAD_WORDS_MAX or any(len(w) > K.BAD_WORD_LEN for w in words):
+        raise ValueError(f"`bad_words_ids`: at most {K.BAD_WORDS_MAX} words of at most {K.BAD_WORD_LEN} tokens each are supported, "
+                         f"got {len(words)} words, the longest of {max(len(w) for w in words)} tokens")
+    return words or None
 
 
 class CachedDecoder:
@@ -330,20 +382,32 @@ class DecodeSession:
     position is captured on first use and replayed afterwards, which removes the ~170 Python->HIP launches per token that
     bound the eager loop."""
 
-    def __init__(self, model, R, S, max_length, nb, ngram, min_length, forced_eos, eos, forced_bos=None):
+    def __init__(self, model, R, S, max_length, nb, ngram, min_length, forced_eos, eos, forced_bos=None, bad_words=None, penalty=1.0):
         self.model, self.R, self.nb, self.max_length = model, R, nb, max_length
         self.ngram, self.min_length, self.forced_eos, self.eos = ngram, min_length, forced_eos, eos
         self.forced_bos = forced_bos
         dev = model.emb16_pad.device
+        # NoBadWords: the table is uploaded once; its bans ride in the ban lists behind the n-gram bans (max_length + n_bad wide)
+        self.bad = K.bad_words_table(bad_words, dev) if bad_words else None
+        self.n_bad = len(bad_words) if bad_words else 0
+        banned = ngram > 0 or self.n_bad > 0
+        # RepetitionPenalty: on the logits for one beam (HF greedy_search), on the log-softmax scores for more (HF beam_search); the
+        # top-k kernels read the histories from the beam state (device bookkeeping) or from hist_s (host loop: uploaded per position)
+        self.penalty = float(penalty)
+        self.pen_rule = None if self.penalty == 1.0 else ("logits" if nb == 1 else "scores")
+        self.hist_s = self.h_hist = None
+        if self.pen_rule:
+            self.hist_s = torch.zeros((R, max_length), device=dev, dtype=torch.int32)
+            self.h_hist = torch.zeros((R, max_length), dtype=torch.int32).pin_memory()
         self.dec = CachedDecoder(model, R, S, max_length, reorders=nb > 1)
         self.ids_s = torch.zeros((R, 1), device=dev, dtype=torch.long)
         self.scores_s = torch.zeros(R, device=dev, dtype=torch.float32)
         self.src_s = torch.zeros(R, device=dev, dtype=torch.long)
-        self.bans_s = torch.full((R, max_length), -1, device=dev, dtype=torch.int32) if ngram > 0 else None
+        self.bans_s = torch.full((R, max_length + self.n_bad), -1, device=dev, dtype=torch.int32) if banned else None
         self.h_ids = torch.zeros((R, 1), dtype=torch.long).pin_memory()
         self.h_scores = torch.zeros(R, dtype=torch.float32).pin_memory()
         self.h_src = torch.zeros(R, dtype=torch.long).pin_memory()
-        self.h_bans = torch.full((R, max_length), -1, dtype=torch.int32).pin_memory() if ngram > 0 else None
+        self.h_bans = torch.full((R, max_length + self.n_bad), -1, dtype=torch.int32).pin_memory() if banned else None
         self.graphs, self.outs, self.pool = {}, {}, None
         # few rows (one caption's beams): the fused LM head + top-k; other shapes: skinny GEMM -> vacnic_beam_topk
         # (the library's own predicate: at V = 50265 the merge's LDS admits 2 nb <= 45, wider beams take the chain)
@@ -375,7 +439,9 @@ class DecodeSession:
                                    next_ids=self.ids_s.data_ptr(), src_idx=self.src_s.data_ptr(),
                                    bans=self.bans_s.data_ptr() if self.bans_s is not None else None,
                                    B=B, nb=nb, Lmax=L, V=self.model.V, eos=self.eos, pad=pad, no_repeat_ngram_size=self.ngram,
-                                   early_stopping=int(bool(early_stopping)), length_penalty=float(length_penalty))
+                                   early_stopping=int(bool(early_stopping)), length_penalty=float(length_penalty),
+                                   bad_words=self.bad[0].data_ptr() if self.bad else None, bad_len=self.bad[1].data_ptr() if self.bad else None,
+                                   n_bad=self.n_bad)
 
     def run_device(self, start, use_graphs):
         """the whole beam search of one batch without per-token host synchronisation; returns the host-side tensors finalize needs."""
@@ -424,23 +490,30 @@ class DecodeSession:
         if self.forced_bos is not None and cur_len == 1:             # ForcedBOSTokenLogitsProcessor (runs before ForcedEOS in HF)
             forced = self.forced_bos if forced < 0 else forced
         V = self.model.V
+        pen = {}
+        if self.pen_rule:
+            pen = dict(history=self.seq[t & 1] if self.beam is not None else self.hist_s, cur_len=cur_len, repetition_penalty=self.penalty,
+                       penalty_rule=self.pen_rule)
         if self.fused_tail:
             # LM head + log_softmax + processors + top-2nb in one C call, no [R, V] logits (a forced position needs no LM head at all)
             hid = self.dec.step(self.ids_s, t, hidden_only=True)
             tv, ti = K.lmhead_topk(hid, self.model.emb16_pad, V, min(2 * self.nb, V), bias=self.model.final_logits_bias.view(-1),
                                    beam_scores=self.scores_s, bans=self.bans_s, eos=self.eos, suppress_eos=cur_len < self.min_length,
-                                   forced_token=forced)
+                                   forced_token=forced, **pen)
         else:
             logits = self.dec.step(self.ids_s, t)
             tv, ti = K.beam_topk(logits, V, min(2 * self.nb, V), beam_scores=self.scores_s, bans=self.bans_s, eos=self.eos,
-                                 suppress_eos=cur_len < self.min_length, forced_token=forced)
+                                 suppress_eos=cur_len < self.min_length, forced_token=forced, **pen)
         if self.beam is not None:
             from . import _lib
             _lib.check(_lib.lib.vacnic_beam_step(_lib.C.byref(self.beam), tv.data_ptr(), ti.data_ptr(), tv.shape[1], cur_len, K._stream()))
         return tv, ti
 
-    def step(self, t, last_tokens, scores, src, bans, use_graphs):
+    def step(self, t, last_tokens, scores, src, bans, use_graphs, seqs=None):
         """host lists in, (top values, top ids) on the host out — the one device->host sync of the position."""
+        if self.pen_rule:
+            self.h_hist[:, :t + 1] = torch.as_tensor(seqs, dtype=torch.int32)
+            self.hist_s.copy_(self.h_hist, non_blocking=True)
         self.h_ids[:, 0] = torch.as_tensor(last_tokens)
         self.ids_s.copy_(self.h_ids, non_blocking=True)
         self.h_scores.copy_(torch.as_tensor(scores, dtype=torch.float32))
@@ -479,10 +552,11 @@ class SampleSession:
     Temperature, top-k, top-p, seed and call counter live in an 8-word device buffer the kernel reads at run time, so the graphs of
     a shape serve every setting.  As in DecodeSession the first caption runs eagerly and later ones replay."""
 
-    def __init__(self, model, R, S, max_length, ngram, min_length, forced_eos, eos, pad, forced_bos=None):
+    def __init__(self, model, R, S, max_length, ngram, min_length, forced_eos, eos, pad, forced_bos=None, bad_words=None):
         self.model, self.R, self.max_length = model, R, max_length
         self.ngram, self.min_length, self.forced_eos, self.eos, self.pad, self.forced_bos = ngram, min_length, forced_eos, eos, pad, forced_bos
         dev = model.emb16_pad.device
+        self.bad = K.bad_words_table(bad_words, dev) if bad_words else None      # uploaded once; its address is part of the captured launches
         self.dec = CachedDecoder(model, R, S, max_length, reorders=False)
         self.ids_s = torch.zeros((R, 1), device=dev, dtype=torch.long)
         self.state = torch.zeros((2, R, max_length), device=dev, dtype=torch.int32)     # histories | log-probs: one copy out at the end
@@ -500,11 +574,12 @@ class SampleSession:
             forced = self.forced_bos if forced < 0 else forced
         logits = self.dec.step(self.ids_s, t)
         K.sample_step(logits, self.model.V, self.params, self.seq, self.done_d, self.ids_s, cur_len, logp=self.logp, eos=self.eos,
-                      pad=self.pad, no_repeat_ngram_size=self.ngram, suppress_eos=cur_len < self.min_length, forced_token=forced)
+                      pad=self.pad, no_repeat_ngram_size=self.ngram, suppress_eos=cur_len < self.min_length, forced_token=forced,
+                      bad_words=self.bad)
 
-    def run(self, start, use_graphs, temperature, top_k, top_p, seed, call):
+    def run(self, start, use_graphs, temperature, top_k, top_p, seed, call, repetition_penalty=1.0):
         """every position enqueued back to back; returns (tokens per row, histories int32 [R, L], log-probs fp32 [R, L]) on the host"""
-        K.sample_params(temperature, top_k, top_p, seed, call, out=self.h_params)
+        K.sample_params(temperature, top_k, top_p, seed, call, out=self.h_params, repetition_penalty=repetition_penalty)
         self.params.copy_(self.h_params, non_blocking=True)
         self.state.zero_()
         self.seq.fill_(self.pad)
@@ -545,6 +620,24 @@ class SampleSession:
 _SAMPLE_CALLS = 0          # per-process count of generate(do_sample=True, seed=None) calls: successive calls draw differently
 _SAMPLE_SESSIONS_MAX = 8   # sampling sessions (KV cache, cross K/V, position graphs) a model keeps: rows = B * num_return_sequences is a
                            # free axis of the key, so the least recently used session goes when a ninth shape arrives
+_DECODE_KEY_LEN = 9        # entries of a DecodeSession key without processors; (bad words, penalty) follow when either is on
+_PROCESSOR_SESSIONS_MAX = 8   # beam / greedy sessions with processors a model keeps (each holds a KV cache and position graphs)
+
+
+def _decode_session_key(R, S, max_length, nb, ngram, min_length, forced_eos, forced_bos, beams, bad_words, penalty):
+    """what a DecodeSession is kept under: the shape and the options baked into its launches; the processors join it only when one
+    is on (the penalty as the float32 the kernels see), so that the default key is the one of before"""
+    key = (R, S, max_length, nb, ngram, min_length, forced_eos, forced_bos, beams)
+    if bad_words or penalty != 1.0:
+        key = key + (bad_words, penalty)
+    return key
+
+
+def _sample_session_key(R, S, max_length, ngram, min_length, forced_eos, forced_bos, bad_words):
+    """what a SampleSession is kept under: no T / top_k / top_p / seed / penalty (run-time parameters of the kernel); the bad-word
+    table's address is part of the captured launches, so the word set joins the key when there is one"""
+    key = (R, S, max_length, ngram, min_length, forced_eos, forced_bos)
+    return key + (bad_words,) if bad_words else key
 
 
 def _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_return_sequences):
@@ -563,7 +656,8 @@ def _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_retu
 
 
 def _generate_sample(model, input_ids, attention_mask, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id,
-                     forced_bos_token_id, enc_args, add_ner_ffn, use_graphs, temperature, top_k, top_p, n, seed, return_logprobs):
+                     forced_bos_token_id, enc_args, add_ner_ffn, use_graphs, temperature, top_k, top_p, n, seed, return_logprobs,
+                     repetition_penalty=1.0, bad_words=None):
     """GenerationMixin.sample of transformers 4.18 (generate(do_sample=True, num_beams=1)): rows b * n + j = sample j of item b."""
     global _SAMPLE_CALLS
     cfg = model.config
@@ -580,18 +674,19 @@ def _generate_sample(model, input_ids, attention_mask, max_length, no_repeat_ngr
     mask_u8 = attention_mask.to(torch.uint8) if attention_mask.dtype != torch.uint8 else attention_mask
     enc_h = _run_encoder(model, use_graphs, add_ner_ffn, input_ids, mask_u8, *enc_args)
     S = enc_h.shape[1]
-    key = (R, S, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id)      # no T / top_k / top_p / seed
+    key = _sample_session_key(R, S, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id, bad_words)
     sessions = model.__dict__.setdefault("_sample_sessions", {})
     ses = sessions.pop(key, None)
     if ses is None:
         while len(sessions) >= _SAMPLE_SESSIONS_MAX:
             sessions.pop(next(iter(sessions)))           # (dicts keep insertion order: the first key is the least recently used)
         ses = SampleSession(model, R, S, max_length, no_repeat_ngram_size, min_length, forced_eos_token_id, eos, pad,
-                            forced_bos=forced_bos_token_id)
+                            forced_bos=forced_bos_token_id, bad_words=bad_words)
     sessions[key] = ses                                  # most recently used last
     ses.dec.begin(enc_h, mask_u8, n)
     try:
-        cur_len, seqs, logps = ses.run(start, use_graphs, float(temperature), int(top_k), float(top_p), seed, call)
+        cur_len, seqs, logps = ses.run(start, use_graphs, float(temperature), int(top_k), float(top_p), seed, call,
+                                       repetition_penalty=float(repetition_penalty))
     except Exception:
         sessions.pop(key, None)                          # its graphs / buffers may hold a half-finished caption
         raise
@@ -743,7 +838,7 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
              no_repeat_ngram_size=0, min_length=0, forced_eos_token_id="config", forced_bos_token_id=None, image_features=None,
              face_features=None, face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, use_graphs=True, device_beams=True,
              return_nbest=False, encoded=None, _after_begin=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-             num_return_sequences=1, seed=None, return_logprobs=False, **unused):
+             num_return_sequences=1, seed=None, return_logprobs=False, repetition_penalty=1.0, bad_words_ids=None, **unused):
     """GenerationMixin.generate(do_sample=False) semantics of transformers 4.18 for this model (greedy = 1 beam).
     Returns int64 [B, L] starting with decoder_start_token_id, padded with pad_token_id.
     Keyword defaults are the LIBRARY defaults; the defaults a hub checkpoint's config.json adds on top (what the reference's
@@ -758,9 +853,17 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
     max_length - 1), then pad; with return_logprobs also fp32 [B * n, L], the log-probability of every token under the distribution
     it was drawn from (0 at the start token and at padding).  seed: an int makes the call reproducible (same inputs, weights and
     seed: same tokens, eager or replayed); None derives one from torch.initial_seed() and a per-process call counter.  With
-    do_sample=False these keywords are ignored."""
+    do_sample=False these keywords are ignored.
+
+    bad_words_ids (NoBadWordsLogitsProcessor of 4.18; every path): a list of token-id lists that must not be generated; [eos] is
+    dropped, at most kernels.BAD_WORDS_MAX words of kernels.BAD_WORD_LEN tokens.  repetition_penalty (a finite number > 0, below 1
+    rewards repetition; RepetitionPenaltyLogitsProcessor): on the raw logits with do_sample=True and with one beam, on the
+    log-softmax scores with more beams, as HF's sample / greedy_search / beam_search apply it (include/vacnic_hip.h has the rules)."""
     if do_sample:
         _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_return_sequences)
+    bad_words = None
+    if bad_words_ids is not None or not (type(repetition_penalty) in (int, float) and repetition_penalty == 1):
+        bad_words = _check_processor_args(model, repetition_penalty, bad_words_ids)
     cfg = model.config
     if model.arena is None:
         raise RuntimeError("call model.finalize(device) first")
@@ -772,7 +875,8 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
             return _generate_sample(model, input_ids, attention_mask, max_length, no_repeat_ngram_size, min_length,
                                     cfg.eos_token_id if forced_eos_token_id == "config" else forced_eos_token_id, forced_bos_token_id,
                                     (image_features, name_ids, name_mask, face_features, face_mask), add_ner_ffn, use_graphs,
-                                    temperature, top_k, top_p, num_return_sequences, seed, return_logprobs)
+                                    temperature, top_k, top_p, num_return_sequences, seed, return_logprobs,
+                                    repetition_penalty=repetition_penalty, bad_words=bad_words)
         finally:
             if was_training:
                 model.train()
@@ -793,13 +897,23 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
         enc_h = _run_encoder(model, use_graphs, add_ner_ffn, input_ids, mask_u8, image_features, name_ids, name_mask, face_features, face_mask)
         S, d = enc_h.shape[1], enc_h.shape[2]
     device_beams = bool(device_beams) and nb <= 16 and 2 * nb * nb <= 128 and max_length <= 512
-    key = (R, S, max_length, nb, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id,
-           (float(length_penalty), bool(early_stopping)) if device_beams else None)
+    penalty = _f32(repetition_penalty)                   # the value the kernels see: 1 + 1e-12 is "off"
+    key = _decode_session_key(R, S, max_length, nb, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id,
+                              (float(length_penalty), bool(early_stopping)) if device_beams else None, bad_words, penalty)
+    processors = len(key) > _DECODE_KEY_LEN
     sessions = model.__dict__.setdefault("_decode_sessions", {})
     ses = sessions.get(key)
+    if ses is not None and processors:
+        sessions[key] = sessions.pop(key)                # most recently used last
     if ses is None:
+        if processors:
+            # the penalty is a free axis of the key: the least recently used processor session goes when a ninth arrives (the
+            # sessions of the default key, which is the shape alone, stay as before)
+            keyed = [k for k in sessions if len(k) > _DECODE_KEY_LEN]
+            for k in keyed[:max(0, len(keyed) - _PROCESSOR_SESSIONS_MAX + 1)]:
+                del sessions[k]
         ses = sessions[key] = DecodeSession(model, R, S, max_length, nb, no_repeat_ngram_size, min_length, forced_eos_token_id, eos,
-                                            forced_bos=forced_bos_token_id)
+                                            forced_bos=forced_bos_token_id, bad_words=bad_words, penalty=penalty)
         if device_beams:
             ses.enable_device_beams(B, length_penalty, early_stopping, pad)
     if encoded is not None:
@@ -851,8 +965,10 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
     while True:
         t = cur_len - 1
         bans = [_banned(s_, no_repeat_ngram_size) for s_ in seqs] if no_repeat_ngram_size > 0 else None
+        if bad_words:
+            bans = [(bans[r] if bans else []) + _bad_word_bans(s_, bad_words) for r, s_ in enumerate(seqs)]
         try:
-            tv, ti = ses.step(t, [s_[-1] for s_ in seqs], beam_scores, new_src, bans, use_graphs)
+            tv, ti = ses.step(t, [s_[-1] for s_ in seqs], beam_scores, new_src, bans, use_graphs, seqs=seqs if ses.pen_rule else None)
         except Exception:
             sessions.pop(key, None)
             if was_training:

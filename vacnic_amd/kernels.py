@@ -1040,16 +1040,29 @@ def probe_layouts():
 
 
 # ------------------------------------------------------------------------------------------------ decode
-def beam_topk(logits, V, K_, beam_scores=None, bans=None, eos=2, suppress_eos=False, forced_token=-1):
+PENALTY_RULES = {None: 0, "logits": 1, "scores": 2}      # penalty_rule of vacnic_beam_topk_ex / vacnic_lmhead_topk
+
+
+def beam_topk(logits, V, K_, beam_scores=None, bans=None, eos=2, suppress_eos=False, forced_token=-1, history=None, cur_len=0,
+              repetition_penalty=1.0, penalty_rule=None):
+    """history int32 [R, >= cur_len] + repetition_penalty + penalty_rule "logits" | "scores": vacnic_beam_topk_ex (include/vacnic_hip.h)"""
     R = logits.shape[0]
     tv = torch.empty((R, K_), device=logits.device, dtype=torch.float32)
     ti = torch.empty((R, K_), device=logits.device, dtype=torch.int32)
+    if penalty_rule is not None:
+        call_struct("vacnic_beam_topk_ex", stream=_stream(), logits=_p(logits), beam_scores=_p(beam_scores), bans=_p(bans), top_val=_p(tv),
+                    top_idx=_p(ti), history=_p(history), R=R, V=V, ldl=logits.stride(0), hist_stride=history.stride(0) if history is not None else 0,
+                    n_ban=bans.shape[1] if bans is not None else 0, eos=eos, suppress_eos=int(suppress_eos), forced_token=forced_token, K=K_,
+                    logits_f32=int(logits.dtype == torch.float32), cur_len=int(cur_len), penalty_rule=PENALTY_RULES[penalty_rule],
+                    penalty=float(repetition_penalty))
+        return tv, ti
     call("vacnic_beam_topk", _p(logits), _p(beam_scores), _p(bans), bans.shape[1] if bans is not None else 0, eos, int(suppress_eos),
          forced_token, _p(tv), _p(ti), R, V, logits.stride(0), K_, int(logits.dtype == torch.float32), _stream())
     return tv, ti
 
 
-def lmhead_topk(h, emb, V, K_, *, bias=None, beam_scores=None, bans=None, eos=2, suppress_eos=False, forced_token=-1, logits=None):
+def lmhead_topk(h, emb, V, K_, *, bias=None, beam_scores=None, bans=None, eos=2, suppress_eos=False, forced_token=-1, logits=None,
+                history=None, cur_len=0, repetition_penalty=1.0, penalty_rule=None):
     """(top values, top ids) [R, K_] of log_softmax(h . emb[:V]^T + bias) after the logits processors, + beam_scores — the LM head
     and vacnic_beam_topk of one decode position without the [R, V] logits (R <= 8, d_model <= 1024).  A forced position
     (forced_token >= 0) computes no logits at all.  logits: optional fp32 [R, >= V] buffer that receives them (diagnostics)."""
@@ -1057,20 +1070,44 @@ def lmhead_topk(h, emb, V, K_, *, bias=None, beam_scores=None, bans=None, eos=2,
     tv = torch.empty((R, K_), device=h.device, dtype=torch.float32)
     ti = torch.empty((R, K_), device=h.device, dtype=torch.int32)
     nws = int(_lib.lib.vacnic_lmhead_topk_workspace(R, V, K_)) if forced_token < 0 else 0
+    pen = {}
+    if penalty_rule is not None:                     # (the scores rule parks the history tokens' logits behind the partial results)
+        pen = dict(history=_p(history), hist_stride=history.stride(0) if history is not None else 0, cur_len=int(cur_len),
+                   penalty_rule=PENALTY_RULES[penalty_rule], penalty=float(repetition_penalty))
+        if penalty_rule == "scores" and forced_token < 0 and history is not None:
+            nws += R * history.stride(0)
     ws = torch.empty(nws, device=h.device, dtype=torch.float32) if nws else None
     call_struct("vacnic_lmhead_topk", stream=_stream(), h=_p(h), emb=_p(emb), bias=_p(bias), logits=_p(logits) if forced_token < 0 else None,
                 workspace=_p(ws), beam_scores=_p(beam_scores), bans=_p(bans), top_val=_p(tv), top_idx=_p(ti), R=R, V=V, d=d, ldw=emb.stride(0),
                 ldl=logits.stride(0) if logits is not None else 0, workspace_floats=nws, n_ban=bans.shape[1] if bans is not None else 0, eos=eos,
-                suppress_eos=int(suppress_eos), forced_token=forced_token, K2=K_)
+                suppress_eos=int(suppress_eos), forced_token=forced_token, K2=K_, **pen)
     return tv, ti
 
 
-def sample_params(temperature=1.0, top_k=0, top_p=1.0, seed=0, call=0, out=None):
+BAD_WORDS_MAX, BAD_WORD_LEN = 1024, 16          # VACNIC_BAD_WORDS_MAX / VACNIC_BAD_WORD_LEN of include/vacnic_hip.h
+
+
+def bad_words_table(words, device="cuda"):
+    """the device bad-word table of include/vacnic_hip.h from a list of token-id lists: (int32 [n, BAD_WORD_LEN] padded with -1,
+    int32 [n] lengths).  The capacity is checked here as the C entry points check it."""
+    n = len(words)
+    if n < 1 or n > BAD_WORDS_MAX or any(not 1 <= len(w) <= BAD_WORD_LEN for w in words):
+        raise ValueError(f"bad_words_table: 1 .. {BAD_WORDS_MAX} words of 1 .. {BAD_WORD_LEN} tokens each")
+    tab = torch.full((n, BAD_WORD_LEN), -1, dtype=torch.int32)
+    for i, w in enumerate(words):
+        tab[i, :len(w)] = torch.tensor([int(t) for t in w], dtype=torch.int32)
+    lens = torch.tensor([len(w) for w in words], dtype=torch.int32)
+    return tab.to(device), lens.to(device)
+
+
+def sample_params(temperature=1.0, top_k=0, top_p=1.0, seed=0, call=0, out=None, repetition_penalty=1.0):
     """the 8-word runtime parameter block of vacnic_sample_step (include/vacnic_hip.h) as a CPU int32 tensor: [T f32, top_k i32,
-    top_p f32, 0, seed low, seed high, call low, call high].  `out`: a (pinned) int32 [8] tensor to fill instead."""
+    top_p f32, repetition penalty f32 (the word stays 0 without one: the kernel reads that as off), seed low, seed high, call low,
+    call high].  `out`: a (pinned) int32 [8] tensor to fill instead."""
     import struct
     seed, call = int(seed) & (2 ** 64 - 1), int(call) & (2 ** 64 - 1)
-    words = struct.unpack("<8i", struct.pack("<fifiIIII", float(temperature), int(top_k), float(top_p), 0, seed & 0xFFFFFFFF, seed >> 32,
+    pen = 0.0 if float(repetition_penalty) == 1.0 else float(repetition_penalty)
+    words = struct.unpack("<8i", struct.pack("<fiffIIII", float(temperature), int(top_k), float(top_p), pen, seed & 0xFFFFFFFF, seed >> 32,
                                              call & 0xFFFFFFFF, call >> 32))
     out = torch.empty(8, dtype=torch.int32) if out is None else out
     out.copy_(torch.tensor(words, dtype=torch.int32))
@@ -1078,15 +1115,17 @@ def sample_params(temperature=1.0, top_k=0, top_p=1.0, seed=0, call=0, out=None)
 
 
 def sample_step(logits, V, params, seq, done, next_ids, cur_len, *, logp=None, eos=2, pad=1, no_repeat_ngram_size=0, suppress_eos=False,
-                forced_token=-1, kept=None, thr=None, mass=None, u=None):
+                forced_token=-1, kept=None, thr=None, mass=None, u=None, bad_words=None):
     """one position of sampling decode for every row: processors -> temperature -> top-k -> top-p -> one Philox draw, and the
     bookkeeping (next_ids int64 [R], seq int32 [R, Lmax] at column cur_len, done int32 [R], logp fp32 [R, Lmax]) in one launch.
-    logits fp32 [R, >= V]; params: int32 [8] on the device (sample_params).  kept / thr / mass / u: optional per-row diagnostics."""
+    logits fp32 [R, >= V]; params: int32 [8] on the device (sample_params).  kept / thr / mass / u: optional per-row diagnostics.
+    bad_words: (table, lengths) from bad_words_table."""
     R = logits.shape[0]
+    bw = {} if bad_words is None else dict(bad_words=_p(bad_words[0]), bad_len=_p(bad_words[1]), n_bad=bad_words[1].shape[0])
     call_struct("vacnic_sample_step", stream=_stream(), logits=_p(logits), params=_p(params), seq=_p(seq), done=_p(done), next_ids=_p(next_ids),
                 logp=_p(logp), kept=_p(kept), thr=_p(thr), mass=_p(mass), u=_p(u), R=R, V=V, ldl=logits.stride(0), Lmax=seq.shape[1],
                 cur_len=int(cur_len), eos=eos, pad=pad, no_repeat_ngram_size=no_repeat_ngram_size, suppress_eos=int(bool(suppress_eos)),
-                forced_token=forced_token)
+                forced_token=forced_token, **bw)
 
 
 def image_u8_normalize(img_u8, flip=None, mean=(0.48145466, 0.4578275, 0.40821073), std=(0.26862954, 0.26130258, 0.27577711)):
@@ -1102,10 +1141,13 @@ def gather_rows(src, dst, idx, rows, row_bytes, row_stride_bytes=0, period=0):
     call("vacnic_gather_rows", _p(src), _p(dst), _p(idx), rows, row_bytes, row_stride_bytes, period, _stream())
 
 
-def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=False, length_penalty=1.0, device="cuda"):
-    """the device state of vacnic_beam_init / vacnic_beam_step (include/vacnic_hip.h) as a namespace of tensors + the C struct `st`."""
+def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=False, length_penalty=1.0, device="cuda", bad_words=None):
+    """the device state of vacnic_beam_init / vacnic_beam_step (include/vacnic_hip.h) as a namespace of tensors + the C struct `st`.
+    bad_words: (table, lengths) from bad_words_table; the ban lists are then Lmax + n_bad wide."""
     import types
     R = B * nb
+    n_bad = 0 if bad_words is None else int(bad_words[1].shape[0])
+    bw = {} if bad_words is None else dict(bad_words=_p(bad_words[0]), bad_len=_p(bad_words[1]), n_bad=n_bad)
     i32 = dict(device=device, dtype=torch.int32)
     s = types.SimpleNamespace(
         B=B, nb=nb, Lmax=Lmax, seq=torch.zeros((2, R, Lmax), **i32), beam_scores=torch.zeros(R, device=device, dtype=torch.float32),
@@ -1113,12 +1155,12 @@ def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=
         hyp_score=torch.zeros((B, nb), device=device, dtype=torch.float64), hyp_len=torch.zeros((B, nb), **i32),
         hyp_seq=torch.zeros((B, nb, Lmax), **i32), next_ids=torch.zeros(R, device=device, dtype=torch.int64),
         src_idx=torch.zeros(R, device=device, dtype=torch.int64),
-        bans=torch.full((R, Lmax), -1, **i32) if no_repeat_ngram_size > 0 else None)
+        bans=torch.full((R, Lmax + n_bad), -1, **i32) if no_repeat_ngram_size > 0 or n_bad > 0 else None, bad_words=bad_words)
     s.st = _lib.BeamState(seq0=s.seq[0].data_ptr(), seq1=s.seq[1].data_ptr(), beam_scores=_p(s.beam_scores), done=_p(s.done),
                           hyp_cnt=_p(s.hyp_cnt), hyp_worst=_p(s.hyp_worst), hyp_score=_p(s.hyp_score), hyp_len=_p(s.hyp_len),
                           hyp_seq=_p(s.hyp_seq), next_ids=_p(s.next_ids), src_idx=_p(s.src_idx), bans=_p(s.bans), B=B, nb=nb, Lmax=Lmax,
                           V=V, eos=eos, pad=pad, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=int(bool(early_stopping)),
-                          length_penalty=float(length_penalty))
+                          length_penalty=float(length_penalty), **bw)
     return s
 
 
