@@ -714,6 +714,55 @@ int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token, void* str
 int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len,
                      void* stream);
 /*
+ * Group (diverse) beam search: transformers 4.18 GenerationMixin.group_beam_search with HammingDiversityLogitsProcessor
+ * (generate(num_beam_groups=G, diversity_penalty=lambda)) on the state of vacnic_beam_init / vacnic_beam_step.  The nb beams of a batch
+ * item are G groups of gs = nb / G: row r = b * nb + g * gs + i is slot i of group g.  The hypothesis list (capacity nb) and the done
+ * flag stay ONE per batch item, shared by its groups, as 4.18's BeamSearchScorer keeps them (later transformers versions keep a list
+ * per group; this is not that).  The top-k kernels run once per position over all R rows exactly as for ordinary beams; the groups
+ * are handled inside ONE launch of vacnic_group_beam_step, one workgroup per batch item, group after group.
+ *
+ * vacnic_group_beam_init: vacnic_beam_init, but slot 0 of EVERY group starts live: beam_scores[r] = 0 for i == 0, else -1e9.
+ * vacnic_group_beam_step(cur_len): per batch item b, for g = 0 .. G - 1 in order, with new_tok[] the tokens chosen so far in this
+ * position:
+ *   1. done[b] set (on entry, or by an earlier group of this position): the group's gs rows get score 0, token pad,
+ *      src_idx = b * nb + g * gs, and ban nothing.  Next group.
+ *   2. Hamming term, for every candidate (v, tok), tok >= 0, of the group's rows: f = #{rows r' of item b in groups < g with
+ *      new_tok[r'] == tok} (a bincount: two earlier beams with the same token count twice).  If f > 0 and forced_token < 0:
+ *      h = fp32(lambda * f); if penalty_rule == 2 and tok occurs in the row's history seq_in[r][0 .. cur_len): h = fp32(h * P);
+ *      v' = fp32(v - h).  Otherwise v' = v.  A forced position (ForcedBOS / ForcedEOS, forced_token >= 0) skips the term: in HF the
+ *      forced processors run after Hamming and overwrite its result.  The factor P is HF's processor order (Hamming, then
+ *      RepetitionPenalty) on log-softmax scores s <= 0: pen(s - lambda f) = (s - lambda f) P = pen(s) - lambda f P.  Rounding: HF
+ *      computes (s - lambda f) + beam_score, this computes (s + beam_score) - lambda f: they differ by at most the last bit.
+ *   3. Merge: the group's candidates ordered (v' desc, i * V + tok asc), the best min(2 gs, K2) kept (G == 1: K2, as
+ *      vacnic_beam_step keeps them).
+ *   4. BeamSearchScorer.process with group_size = gs over those in rank order: EOS at rank >= gs is skipped; EOS at rank < gs adds
+ *      (history of its row, v') to the item's shared list, scored (double)v' / cur_len^length_penalty (the host's pow); any other
+ *      candidate continues, until gs continue.
+ *   5. done[b] |= (list length >= nb) && (early_stopping || worst >= best_v' / cur_len^length_penalty), best_v' = rank 0 of THIS
+ *      group's merged list.
+ *   6. The group's rows: history (source row's + token), beam_scores, next_ids, src_idx (always a row of the same group), and the
+ *      NoRepeatNGram / bad-word bans of the next position exactly as vacnic_beam_step writes them.
+ * Why the per-row lists of K2 = min(2 nb, V) suffice (the top-k kernels need no change): the term only lowers scores, and lowers at
+ * most nb - gs distinct tokens per row, so a row's list of 2 nb still holds at least nb + gs >= 2 gs unlowered entries; each of those
+ * is at least as large as any unlisted token of the row, and on equal score the listed token has the lower id.  So the group's true
+ * top 2 gs after the penalty lies inside the union of its rows' lists.
+ * With num_beam_groups == 1 both calls leave the state bit for bit as vacnic_beam_init / vacnic_beam_step do (diversity_penalty,
+ * repetition_penalty, penalty_rule and forced_token are then unused but still checked).
+ * Shapes: those of vacnic_beam_step (nb <= 16, nb * K2 <= 128, Lmax <= 512; otherwise VACNIC_UNSUPPORTED).  VACNIC_BAD_SHAPE: as
+ * vacnic_beam_init / vacnic_beam_step; num_beam_groups < 1 or not dividing nb; diversity_penalty negative or not finite;
+ * repetition_penalty not a finite number > 0; penalty_rule outside {0, 2}.  All decided before any launch.
+ */
+typedef struct {
+  int32_t num_beam_groups;      /* G */
+  float diversity_penalty;      /* lambda >= 0; 0 = groups without the Hamming term */
+  float repetition_penalty;     /* P of the top-k call of this position (read only under penalty_rule 2) */
+  int32_t penalty_rule;         /* 0 = no repetition penalty, 2 = on the scores (vacnic_beam_topk_ex) */
+  int32_t forced_token;         /* forced_token of the top-k call of this position (-1 = none) */
+} vacnic_group_beam_args;
+int vacnic_group_beam_init(const vacnic_beam_state* st, const vacnic_group_beam_args* ga, int32_t start_token, void* stream);
+int vacnic_group_beam_step(const vacnic_beam_state* st, const vacnic_group_beam_args* ga, const float* top_val, const int32_t* top_idx,
+                           int32_t K2, int32_t cur_len, void* stream);
+/*
  * Sampling decode, one position (transformers 4.18 GenerationMixin.sample: processors on the raw logits, then the warpers
  * temperature -> top-k -> top-p, then softmax and one draw) with the bookkeeping of the position: one launch, one workgroup per
  * row, no host round trip.  Everything below is exact enough to be replayed on the host (tests/test_sample.py does).

@@ -2,11 +2,12 @@
 run_full_train.sh:10), beam 5, max_length 50, length_penalty 2.0, seed 42; synthetic GoodNews-shaped inputs.
 
     bench_generate.py [n] [batch] [--num_beams N] [--do_sample [--top_k K] [--top_p P] [--temperature T] [--num_return_sequences N]]
-                      [--repetition_penalty P] [--bad_words 3,4;50264]
+                      [--repetition_penalty P] [--bad_words 3,4;50264] [--num_beam_groups G --diversity_penalty L]
 
 --do_sample times sampling decode at the same shape (one beam; rows = batch x num_return_sequences); --num_beams 1 is the greedy
 decode it goes beside.  --repetition_penalty / --bad_words (comma-separated ids, `;` between words) switch the two logits
-processors on; without them the calls are the ones of before.
+processors on; without them the calls are the ones of before.  --num_beam_groups / --diversity_penalty: group (diverse) beam search
+(G has to divide --num_beams); one group is the beam search of before.
 
     bench_generate.py --kernel [--rows 1,8] [--vocab 50265]
 
@@ -89,6 +90,8 @@ def main():
     ap.add_argument("--num_return_sequences", type=int, default=1)
     ap.add_argument("--repetition_penalty", type=float, default=1.0)
     ap.add_argument("--bad_words", default="")
+    ap.add_argument("--num_beam_groups", type=int, default=1)
+    ap.add_argument("--diversity_penalty", type=float, default=0.0)
     a = ap.parse_args()
     if a.kernel:
         return kernel_mode([int(r) for r in a.rows.split(",")], a.vocab)
@@ -100,6 +103,9 @@ def main():
     else:
         mode = dict(num_beams=a.num_beams, length_penalty=2.0)
         what = f"beam {a.num_beams}"
+    if a.num_beam_groups != 1 or a.diversity_penalty != 0.0:
+        mode.update(num_beam_groups=a.num_beam_groups, diversity_penalty=a.diversity_penalty)
+        what += f", {a.num_beam_groups} groups, diversity_penalty {a.diversity_penalty}"
     if a.repetition_penalty != 1.0:
         mode["repetition_penalty"] = a.repetition_penalty
         what += f", repetition_penalty {a.repetition_penalty}"

@@ -139,6 +139,9 @@ BeamState = _struct("vacnic_beam_state", [
     ("B", i64), ("nb", i64), ("Lmax", i64), ("V", i64), ("eos", i64), ("pad", i64), ("no_repeat_ngram_size", i64), ("early_stopping", i64),
     ("length_penalty", f32), ("bad_words", vp), ("bad_len", vp), ("n_bad", i64)])
 
+GroupBeamArgs = _struct("vacnic_group_beam_args", [
+    ("num_beam_groups", i32), ("diversity_penalty", f32), ("repetition_penalty", f32), ("penalty_rule", i32), ("forced_token", i32)])
+
 LmheadTopkArgs = _struct("vacnic_lmhead_topk_args", [
     ("h", vp), ("emb", vp), ("bias", vp), ("logits", vp), ("workspace", vp), ("beam_scores", vp), ("bans", vp), ("top_val", vp), ("top_idx", vp),
     ("R", i64), ("V", i64), ("d", i64), ("ldw", i64), ("ldl", i64), ("workspace_floats", i64),
@@ -265,6 +268,8 @@ _PLAIN_FNS = {
     "vacnic_comm_broadcast": [i64, vp, i64, i32, i32, vp], "vacnic_comm_destroy": [i64],
     "vacnic_event_record": [i32, vp], "vacnic_event_wait": [i32, vp],
     "vacnic_beam_step": [C.POINTER(BeamState), vp, vp, i32, i32, vp],
+    "vacnic_group_beam_init": [C.POINTER(BeamState), C.POINTER(GroupBeamArgs), i32, vp],
+    "vacnic_group_beam_step": [C.POINTER(BeamState), C.POINTER(GroupBeamArgs), vp, vp, i32, i32, vp],
 }
 EXPORTED = sorted(list(_STRUCT_FNS) + list(_PLAIN_FNS) + ["vacnic_last_error_string", "vacnic_version", "vacnic_decoder_step_sync_bytes", "vacnic_decoder_step_slots_bytes",
                                                             "vacnic_plan_begin", "vacnic_plan_size", "vacnic_plan_mark",

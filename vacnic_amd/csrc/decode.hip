@@ -908,12 +908,229 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(BeamP p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Group (diverse) beam search: the bookkeeping of one position for G groups of gs = nb / G beams (include/vacnic_hip.h at
+// vacnic_group_beam_step has the rules).  beam_step_kernel's structure, with the merge + BeamSearchScorer.process run once per
+// group, in order, inside the launch: group g reads the tokens the earlier groups chose (ntok[0 .. g gs)) from LDS for the Hamming
+// term, and the done flag an earlier group of the same position set.  The history / ban writers run once, for all nb rows, behind
+// the last group.  With G == 1 every value written is beam_step_kernel's.
+struct GroupP {
+  BeamP b;
+  int G, forced, pen_on;          // pen_on: the repetition penalty is on the scores (rule 2) and P != 1
+  float lambda, P;
+};
+
+// wave-wide arg-best of (index bi >= 0, value bv, key bk) by (value desc, key asc): beam_step_kernel's DPP ladder (quad xor 1, xor 2,
+// mirror within 8, mirror within 16) + a scalar pass over the four rows.  Every lane returns the winner; bi < 0 = the lane has none.
+__device__ __forceinline__ void wave_arg_best(int& bi, float& bv, long long& bk) {
+  int bh = (int)(bk >> 32), bl = (int)(bk & 0xffffffffLL);
+#define VAC_STEP(CTRL_)                                                                                                          \
+  {                                                                                                                              \
+    const int oi = __builtin_amdgcn_update_dpp(0, bi, CTRL_, 0xf, 0xf, true);                                                   \
+    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, bv), CTRL_, 0xf, 0xf, true)); \
+    const int oh = __builtin_amdgcn_update_dpp(0, bh, CTRL_, 0xf, 0xf, true), ol = __builtin_amdgcn_update_dpp(0, bl, CTRL_, 0xf, 0xf, true); \
+    const long long ok = ((long long)oh << 32) | (unsigned)ol, mk = ((long long)bh << 32) | (unsigned)bl;                        \
+    if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && ok < mk))) { bi = oi; bv = ov; bh = oh; bl = ol; }                         \
+  }
+  VAC_STEP(0xB1) VAC_STEP(0x4E) VAC_STEP(0x141) VAC_STEP(0x140)
+#undef VAC_STEP
+  int ri_ = __builtin_amdgcn_readlane(bi, 0), rh_ = __builtin_amdgcn_readlane(bh, 0), rl_ = __builtin_amdgcn_readlane(bl, 0);
+  float rv_ = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv), 0));
+#pragma unroll
+  for (int row = 1; row < 4; ++row) {
+    const int oi = __builtin_amdgcn_readlane(bi, 16 * row), oh = __builtin_amdgcn_readlane(bh, 16 * row), ol = __builtin_amdgcn_readlane(bl, 16 * row);
+    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bv), 16 * row));
+    const long long ok = ((long long)oh << 32) | (unsigned)ol, mk = ((long long)rh_ << 32) | (unsigned)rl_;
+    if (oi >= 0 && (ri_ < 0 || ov > rv_ || (ov == rv_ && ok < mk))) { ri_ = oi; rv_ = ov; rh_ = oh; rl_ = ol; }
+  }
+  bi = ri_; bv = rv_; bk = ((long long)rh_ << 32) | (unsigned)rl_;
+}
+
+// v' of one candidate of group g: v - lambda f [P if the token is in the row's history], f = how many rows of the earlier groups
+// chose `tok` in this position (ntok[0 .. n_prev)).  Every operation is rounded on its own (no fused multiply-add): the host model
+// of the tests replays it.
+__device__ __forceinline__ float hamming_term(const GroupP& p, float v, int tok, const int* ntok, int n_prev, const int32_t* hist, int cur) {
+  int f = 0;
+  for (int i = 0; i < n_prev; ++i) f += ntok[i] == tok;
+  if (f == 0) return v;
+  float h = __fmul_rn(p.lambda, (float)f);
+  if (p.pen_on) {
+    // a serial scan of <= 512 history tokens from global memory by every lane with f > 0 (at most nb - gs tokens per row): the rows'
+    // K2 lanes share one history, so staging the group's histories in LDS (as the writers below do) is the first thing to try if
+    // this is to be made cheaper: groups with a repetition penalty cost ~10 us per position over the penalty alone at max_length 50,
+    // groups without one nothing measurable (profiles/group_beam.txt)
+    bool in_hist = false;
+    for (int i = 0; i < cur; ++i) in_hist = in_hist || hist[i] == tok;
+    if (in_hist) h = __fmul_rn(h, p.P);
+  }
+  return __fsub_rn(v, h);
+}
+
+__global__ __launch_bounds__(1024) void group_beam_step_kernel(GroupP gp) {
+  const BeamP& p = gp.b;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nthr = blockDim.x;
+  const int nb = p.nb, K2 = p.K2, L = p.Lmax, cur = p.cur_len, G = gp.G, gs = nb / G;
+  const int nkeep = G == 1 ? K2 : (K2 < 2 * gs ? K2 : 2 * gs);      // <= 64 (K2 <= 64)
+  __shared__ float cs[64]; __shared__ int cj[64], ct[64];          // the current group's merged candidates, in rank order
+  __shared__ float nsc[32]; __shared__ int ntok[32], nsrc[32];      // the nb continuing beams, group after group
+  __shared__ int gpad[16];                                          // group g was padded along (the item was finished): its rows ban nothing
+  __shared__ int hyp_from[288]; __shared__ int hyp_slot[288]; __shared__ int n_hyp_copy;   // <= nb adds x (nb - 1 shifts + 1) per position
+  __shared__ int is_done, nsel_s;
+  if (tid == 0) { n_hyp_copy = 0; is_done = p.done[b]; nsel_s = 0; }
+  __syncthreads();
+  for (int g = 0; g < G; ++g) {
+    if (!is_done && wv == 0) {
+      // ---- merge the group's per-beam lists with the Hamming term applied: order (v' desc, slot * V + token asc), keep nkeep
+      const int ncand = gs * K2;                                    // <= 128: every lane owns up to two candidates
+      const size_t base = ((size_t)b * nb + (size_t)g * gs) * K2;
+      float v0 = 0.f, v1 = 0.f; long long k0 = 0, k1 = 0; int t0 = -1, t1 = -1;
+      if (lane < ncand) { t0 = p.top_idx[base + lane]; v0 = p.top_val[base + lane]; k0 = (long long)(lane / K2) * p.V + t0; }
+      if (lane + 64 < ncand) { t1 = p.top_idx[base + lane + 64]; v1 = p.top_val[base + lane + 64]; k1 = (long long)((lane + 64) / K2) * p.V + t1; }
+      if (g > 0 && gp.forced < 0) {
+        const int32_t* hist = p.seq_in + ((size_t)b * nb + (size_t)g * gs) * L;
+        if (t0 >= 0) v0 = hamming_term(gp, v0, t0, ntok, g * gs, hist + (size_t)(lane / K2) * L, cur);
+        if (t1 >= 0) v1 = hamming_term(gp, v1, t1, ntok, g * gs, hist + (size_t)((lane + 64) / K2) * L, cur);
+      }
+      bool u0 = t0 < 0, u1 = t1 < 0;
+      for (int r = 0; r < nkeep; ++r) {
+        int bi = -1; float bv = 0.f; long long bk = 0;                // this lane's best unused candidate
+        if (!u0) { bi = lane; bv = v0; bk = k0; }
+        if (!u1 && (bi < 0 || v1 > bv || (v1 == bv && k1 < bk))) { bi = lane + 64; bv = v1; bk = k1; }
+        wave_arg_best(bi, bv, bk);
+        if (bi < 0) break;                                    // wave-uniform
+        if (bi == lane) u0 = true;
+        if (bi == lane + 64) u1 = true;
+        if (lane == 0) { cs[r] = bv; cj[r] = g * gs + bi / K2; ct[r] = (int)(bk - (long long)(bi / K2) * p.V); nsel_s = r + 1; }
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int j0 = g * gs;
+      gpad[g] = is_done;
+      if (!is_done) {
+        const int nsel = nsel_s;
+        // ---- BeamSearchScorer.process with group_size = gs, on the item's shared list (capacity nb)
+        const double lenpow = p.lenpow;
+        int cnt = p.hyp_cnt[b]; double worst = p.hyp_worst[b];
+        int nch = 0;
+        for (int r = 0; r < nsel && nch < gs; ++r) {
+          if (ct[r] == p.eos) {
+            if (r >= gs) continue;
+            const double score = (double)cs[r] / lenpow;
+            if (cnt < nb || score > worst) {                                  // _BeamHyps.add
+              int slot = cnt;
+              if (cnt == nb) {
+                // list full: append, then drop the lowest score (lowest index among ties) -> compact in list order
+                int lo = 0;
+                for (int i = 1; i < nb; ++i) if (p.hyp_score[(size_t)b * nb + i] < p.hyp_score[(size_t)b * nb + lo]) lo = i;
+                const bool drop_new = score < p.hyp_score[(size_t)b * nb + lo];     // cannot happen (score > worst), kept for symmetry
+                if (!drop_new) {
+                  for (int i = lo; i + 1 < nb; ++i) {
+                    p.hyp_score[(size_t)b * nb + i] = p.hyp_score[(size_t)b * nb + i + 1];
+                    p.hyp_len[(size_t)b * nb + i] = p.hyp_len[(size_t)b * nb + i + 1];
+                    hyp_from[n_hyp_copy] = -(i + 1) - 1; hyp_slot[n_hyp_copy] = i; ++n_hyp_copy;   // slot i+1 -> i, done by all lanes below, in order
+                  }
+                  slot = nb - 1;
+                } else {
+                  slot = -1;
+                }
+              }
+              if (slot >= 0) {
+                p.hyp_score[(size_t)b * nb + slot] = score;
+                p.hyp_len[(size_t)b * nb + slot] = cur;
+                hyp_from[n_hyp_copy] = b * nb + cj[r]; hyp_slot[n_hyp_copy] = slot; ++n_hyp_copy;      // copy seq_in[row] -> hyp_seq[slot]
+                if (cnt < nb) ++cnt;
+                worst = p.hyp_score[(size_t)b * nb];
+                for (int i = 1; i < cnt; ++i) worst = fmin(worst, p.hyp_score[(size_t)b * nb + i]);
+              }
+            }
+          } else {
+            nsc[j0 + nch] = cs[r]; ntok[j0 + nch] = ct[r]; nsrc[j0 + nch] = b * nb + cj[r]; ++nch;
+          }
+        }
+        p.hyp_cnt[b] = cnt; p.hyp_worst[b] = worst;
+        // is_done(best_sum_logprobs = best candidate of THIS group, cur_len); the groups behind this one see the flag in this position
+        bool dn = false;
+        if (cnt >= nb && nsel > 0) dn = p.early ? true : (worst >= (double)cs[0] / lenpow);     // (no candidate at all: cs[0] is not this group's)
+        if (dn) { p.done[b] = 1; is_done = 1; }
+        for (; nch < gs; ++nch) { nsc[j0 + nch] = -1e9f; ntok[j0 + nch] = p.pad; nsrc[j0 + nch] = b * nb + j0; }   // fewer than 2 gs candidates only
+      } else {
+        for (int j = j0; j < j0 + gs; ++j) { nsc[j] = 0.f; ntok[j] = p.pad; nsrc[j] = b * nb + j0; }   // finished item: padded along
+      }
+      nsel_s = 0;
+    }
+    __syncthreads();
+  }
+  // ---- finished-hypothesis sequence moves, in the order they were queued (a shift reads a slot a later entry overwrites)
+  for (int c = 0; c < n_hyp_copy; ++c) {
+    const int from = hyp_from[c], slot = hyp_slot[c];
+    const int32_t* src = from < 0 ? p.hyp_seq + ((size_t)b * nb + (-from - 1)) * L : p.seq_in + (size_t)from * L;
+    int32_t* dst = p.hyp_seq + ((size_t)b * nb + slot) * L;
+    int32_t tmp[8];                                     // L <= 512, >= 64 threads
+    int n = 0;
+    for (int i = tid; i < L; i += nthr) tmp[n++] = src[i];
+    __syncthreads();
+    n = 0;
+    for (int i = tid; i < L; i += nthr) dst[i] = tmp[n++];
+    __syncthreads();
+  }
+  // ---- the nb continuing beams, one wave each, as in beam_step_kernel: history + new token (kept in LDS for the ban search), score,
+  // source row, last token; then the NoRepeatNGram and bad-word bans of the next position (none for the rows of a padded group)
+  __shared__ int sseq[16][512];
+  __shared__ int nban[16];
+  if (wv < nb) {
+    const int j = wv, row = b * nb + j;
+    const bool padded = gpad[j / gs] != 0;
+    const int32_t* src = p.seq_in + (size_t)nsrc[j] * L;
+    int32_t* dst = p.seq_out + (size_t)row * L;
+    if (lane == 0) nban[j] = 0;
+    for (int i = lane; i < L; i += 64) {
+      const int v = i < cur ? src[i] : (i == cur ? ntok[j] : p.pad);
+      dst[i] = v;
+      sseq[j][i] = v;
+    }
+    if (lane == 0) {
+      p.beam_scores[row] = nsc[j];
+      p.next_ids[row] = ntok[j];
+      p.src_idx[row] = nsrc[j];
+    }
+    if (p.bans) {
+      // (a wave's LDS operations execute in order: the history written above is visible to all its lanes here)
+      const int n = p.ngram, len = cur + 1;               // histories now hold cur + 1 tokens
+      const int* sq = sseq[j];
+      const int nbw = L + p.n_bad;
+      int32_t* bn = p.bans + (size_t)row * nbw;
+      if (n > 0 && len + 1 >= n && !padded) {
+        for (int i = lane; i <= len - n; i += 64) {
+          bool match = true;
+          for (int k = 0; k < n - 1; ++k) match = match && sq[i + k] == sq[len - (n - 1) + k];
+          if (match) bn[atomicAdd(&nban[j], 1)] = sq[i + n - 1];
+        }
+      }
+      if (!padded) {
+        for (int w = lane; w < p.n_bad; w += 64) {
+          const int m = p.bad_len[w];
+          if (m < 1 || m > VACNIC_BAD_WORD_LEN || m - 1 > len) continue;
+          const int32_t* bw = p.bad_words + (size_t)w * VACNIC_BAD_WORD_LEN;
+          bool match = true;
+          for (int k = 0; k < m - 1; ++k) match = match && bw[k] == sq[len - (m - 1) + k];
+          const int t = bw[m - 1];
+          if (match && t >= 0 && t < p.V) bn[atomicAdd(&nban[j], 1)] = t;
+        }
+      }
+      const int nb_ = nban[j];
+      for (int i = nb_ + lane; i < nbw; i += 64) bn[i] = -1;
+    }
+  }
+}
+
+// gs: beams per group (nb for ordinary beam search): slot 0 of every group starts live
 __global__ void beam_init_kernel(int32_t* seq, float* beam_scores, int32_t* done, int32_t* hyp_cnt, double* hyp_worst, int64_t* next_ids,
-                                 int32_t* bans, int R, int nb, int L, int start, int pad, int n_bad) {
+                                 int32_t* bans, int R, int nb, int L, int start, int pad, int n_bad, int gs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < R * L) seq[i] = (i % L) == 0 ? start : pad;
   if (i < R * (L + n_bad) && bans) bans[i] = -1;
-  if (i < R) { beam_scores[i] = (i % nb) == 0 ? 0.f : -1e9f; next_ids[i] = start; }
+  if (i < R) { beam_scores[i] = (i % gs) == 0 ? 0.f : -1e9f; next_ids[i] = start; }
   if (i < R / nb) { done[i] = 0; hyp_cnt[i] = 0; hyp_worst[i] = 1e9; }
 }
 
@@ -1112,8 +1329,8 @@ extern "C" int vacnic_gather_rows(const void* src, void* dst, const int64_t* idx
   return VACNIC_OK;
 }
 
-extern "C" int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token, void* stream) {
-  VPLAN_REC_STRUCT(vacnic_beam_init, st, start_token, stream);
+// vacnic_beam_init for groups of gs beams (gs == nb: ordinary beam search)
+static int beam_init_checked(const vacnic_beam_state* st, int32_t start_token, int gs, void* stream) {
   VCHECK(st && st->seq[0] && st->beam_scores && st->done && st->hyp_cnt && st->hyp_worst && st->next_ids, VACNIC_BAD_SHAPE, "beam_init: null state");
   VCHECK(st->B > 0 && st->nb > 0 && st->Lmax > 0, VACNIC_BAD_SHAPE, "beam_init: bad sizes");
   VCHECK(st->n_bad >= 0 && st->n_bad <= VACNIC_BAD_WORDS_MAX, VACNIC_UNSUPPORTED, "beam_init: %ld bad words, at most %d", (long)st->n_bad,
@@ -1124,7 +1341,7 @@ extern "C" int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token
   const int n = R * nbw;
   hipLaunchKernelGGL(beam_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, st->seq[0], st->beam_scores,
                      st->done, st->hyp_cnt, st->hyp_worst, st->next_ids, st->bans, R, (int)st->nb, (int)st->Lmax, start_token, (int)st->pad,
-                     (int)st->n_bad);
+                     (int)st->n_bad, gs > 0 ? gs : (int)st->nb);
   VLAUNCH_CHECK();
   if (st->n_bad > 0) {
     hipLaunchKernelGGL(beam_init_bad_words_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, st->bans, st->bad_words, st->bad_len,
@@ -1134,9 +1351,36 @@ extern "C" int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token
   return VACNIC_OK;
 }
 
-extern "C" int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len,
-                                void* stream) {
-  VPLAN_REC_STRUCT(vacnic_beam_step, st, top_val, top_idx, K2, cur_len, stream);
+extern "C" int vacnic_beam_init(const vacnic_beam_state* st, int32_t start_token, void* stream) {
+  VPLAN_REC_STRUCT(vacnic_beam_init, st, start_token, stream);
+  return beam_init_checked(st, start_token, 0, stream);
+}
+
+// the checks on vacnic_group_beam_args that init and step share (nb is known to be >= 1)
+static int group_args_checked(const vacnic_group_beam_args* ga, long nb, const char* who) {
+  VCHECK(ga->num_beam_groups >= 1 && nb % ga->num_beam_groups == 0, VACNIC_BAD_SHAPE, "%s: num_beam_groups %d must be >= 1 and divide nb = %ld", who,
+         (int)ga->num_beam_groups, nb);
+  VCHECK(ga->diversity_penalty >= 0.f && ga->diversity_penalty <= 3.4028234e38f, VACNIC_BAD_SHAPE, "%s: the diversity penalty must be a finite number >= 0", who);
+  VCHECK(ga->repetition_penalty > 0.f && ga->repetition_penalty <= 3.4028234e38f, VACNIC_BAD_SHAPE, "%s: the repetition penalty must be a finite number > 0", who);
+  VCHECK(ga->penalty_rule == 0 || ga->penalty_rule == 2, VACNIC_BAD_SHAPE, "%s: penalty_rule %d outside {0, 2}", who, (int)ga->penalty_rule);
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_group_beam_init(const vacnic_beam_state* st, const vacnic_group_beam_args* ga, int32_t start_token, void* stream) {
+  vplan::Guard vplan_guard__;
+  if (vplan::outermost() && st && ga) {
+    const vacnic_beam_state st_ = *st; const vacnic_group_beam_args ga_ = *ga;
+    vplan::push([=]() { return vacnic_group_beam_init(&st_, &ga_, start_token, stream); });
+  }
+  VCHECK(st && ga, VACNIC_BAD_SHAPE, "group_beam_init: null operand");
+  VCHECK(st->nb > 0, VACNIC_BAD_SHAPE, "group_beam_init: bad sizes");
+  const int rc = group_args_checked(ga, (long)st->nb, "group_beam_init");
+  if (rc != VACNIC_OK) return rc;
+  return beam_init_checked(st, start_token, (int)(st->nb / ga->num_beam_groups), stream);
+}
+
+// the checks of vacnic_beam_step and the kernel arguments built from the state
+static int beam_step_params(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len, BeamP* out) {
   VCHECK(st && top_val && top_idx && st->seq[0] && st->seq[1] && st->hyp_score && st->hyp_len && st->hyp_seq && st->src_idx,
          VACNIC_BAD_SHAPE, "beam_step: null operand");
   VCHECK(st->nb >= 1 && st->nb <= 16 && K2 >= 1 && K2 <= 64 && st->nb * K2 <= 128, VACNIC_UNSUPPORTED, "beam_step: nb <= 16, K2 <= 64, nb*K2 <= 128");
@@ -1153,7 +1397,38 @@ extern "C" int vacnic_beam_step(const vacnic_beam_state* st, const float* top_va
   p.nb = (int)st->nb; p.K2 = K2; p.Lmax = (int)st->Lmax; p.cur_len = cur_len; p.V = (int)st->V; p.eos = (int)st->eos; p.pad = (int)st->pad;
   p.bad_words = st->bad_words; p.bad_len = st->bad_len; p.n_bad = (int)st->n_bad;
   p.ngram = (int)st->no_repeat_ngram_size; p.early = (int)st->early_stopping; p.lenpow = pow((double)cur_len, (double)st->length_penalty);
+  *out = p;
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_beam_step(const vacnic_beam_state* st, const float* top_val, const int32_t* top_idx, int32_t K2, int32_t cur_len,
+                                void* stream) {
+  VPLAN_REC_STRUCT(vacnic_beam_step, st, top_val, top_idx, K2, cur_len, stream);
+  BeamP p;
+  const int rc = beam_step_params(st, top_val, top_idx, K2, cur_len, &p);
+  if (rc != VACNIC_OK) return rc;
   hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)st->B), dim3((unsigned)(64 * st->nb)), 0, (hipStream_t)stream, p);
+  VLAUNCH_CHECK();
+  return VACNIC_OK;
+}
+
+extern "C" int vacnic_group_beam_step(const vacnic_beam_state* st, const vacnic_group_beam_args* ga, const float* top_val, const int32_t* top_idx,
+                                      int32_t K2, int32_t cur_len, void* stream) {
+  vplan::Guard vplan_guard__;
+  if (vplan::outermost() && st && ga) {
+    const vacnic_beam_state st_ = *st; const vacnic_group_beam_args ga_ = *ga;
+    vplan::push([=]() { return vacnic_group_beam_step(&st_, &ga_, top_val, top_idx, K2, cur_len, stream); });
+  }
+  VCHECK(ga, VACNIC_BAD_SHAPE, "group_beam_step: null operand");
+  GroupP gp;
+  int rc = beam_step_params(st, top_val, top_idx, K2, cur_len, &gp.b);
+  if (rc != VACNIC_OK) return rc;
+  rc = group_args_checked(ga, (long)st->nb, "group_beam_step");
+  if (rc != VACNIC_OK) return rc;
+  VCHECK(ga->forced_token < st->V, VACNIC_BAD_SHAPE, "group_beam_step: forced_token %d outside the vocabulary", (int)ga->forced_token);
+  gp.G = ga->num_beam_groups; gp.forced = ga->forced_token < 0 ? -1 : ga->forced_token;
+  gp.lambda = ga->diversity_penalty; gp.P = ga->repetition_penalty; gp.pen_on = ga->penalty_rule == 2 && ga->repetition_penalty != 1.f;
+  hipLaunchKernelGGL(group_beam_step_kernel, dim3((unsigned)st->B), dim3((unsigned)(64 * st->nb)), 0, (hipStream_t)stream, gp);
   VLAUNCH_CHECK();
   return VACNIC_OK;
 }

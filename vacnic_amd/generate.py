@@ -17,6 +17,9 @@ What runs where
     are appended to the ban lists by `vacnic_beam_init` / `vacnic_beam_step` (host loop: `_bad_word_bans`) and matched in place by
     `vacnic_sample_step`; the penalty is applied by the top-k kernels from the token histories (on the logits for one beam and for
     sampling, on the log-softmax scores for more beams).  Off (1.0 / None) the calls are the ones of before.
+  * group (diverse) beam search (`num_beam_groups` > 1, `diversity_penalty`; 4.18's group_beam_search + HammingDiversity): the same
+    per-position tail over all rows, then `vacnic_group_beam_step` in place of `vacnic_beam_step` — the groups of an item in order
+    inside one launch (host loop: the same rules in generate()).  One group (the default): the calls are the ones of before.
 
 The cache is preallocated ([layers, B*beams, max_length, 2d] bf16, k|v interleaved per row) instead of the reference's
 per-step torch.cat (MFULL:489-492).
@@ -382,8 +385,12 @@ class DecodeSession:
     position is captured on first use and replayed afterwards, which removes the ~170 Python->HIP launches per token that
     bound the eager loop."""
 
-    def __init__(self, model, R, S, max_length, nb, ngram, min_length, forced_eos, eos, forced_bos=None, bad_words=None, penalty=1.0):
+    def __init__(self, model, R, S, max_length, nb, ngram, min_length, forced_eos, eos, forced_bos=None, bad_words=None, penalty=1.0,
+                 groups=None):
         self.model, self.R, self.nb, self.max_length = model, R, nb, max_length
+        # group (diverse) beam search: (num_beam_groups, diversity_penalty) with more than one group, else None — the position's tail is
+        # the same call; vacnic_group_beam_step takes the place of vacnic_beam_step behind it
+        self.groups = (int(groups[0]), float(groups[1])) if groups and int(groups[0]) > 1 else None
         self.ngram, self.min_length, self.forced_eos, self.eos = ngram, min_length, forced_eos, eos
         self.forced_bos = forced_bos
         dev = model.emb16_pad.device
@@ -447,7 +454,11 @@ class DecodeSession:
         """the whole beam search of one batch without per-token host synchronisation; returns the host-side tensors finalize needs."""
         from . import _lib
         st = K._stream()
-        _lib.check(_lib.lib.vacnic_beam_init(_lib.C.byref(self.beam), int(start), st))
+        if self.groups:
+            ga = K.group_beam_args(self.groups)
+            _lib.check(_lib.lib.vacnic_group_beam_init(_lib.C.byref(self.beam), _lib.C.byref(ga), int(start), st))
+        else:
+            _lib.check(_lib.lib.vacnic_beam_init(_lib.C.byref(self.beam), int(start), st))
         steps = 0
         pending = None                                       # (event, pinned copy of the done flags): polled without blocking the launches
         for t in range(self.max_length - 1):
@@ -482,13 +493,18 @@ class DecodeSession:
         return (cur_len, seqs, self.scores_s.cpu(), self.done_d.cpu(), self.hyp_cnt.cpu(), self.hyp_score.cpu(), self.hyp_len.cpu(),
                 self.hyp_seq.cpu())
 
+    def forced_at(self, cur_len):
+        """the forced token of the position whose histories hold cur_len tokens, or -1"""
+        forced = self.forced_eos if (self.forced_eos is not None and cur_len == self.max_length - 1) else -1
+        if self.forced_bos is not None and cur_len == 1:             # ForcedBOSTokenLogitsProcessor (runs before ForcedEOS in HF)
+            forced = self.forced_bos if forced < 0 else forced
+        return forced
+
     def body(self, t):
         if self.nb > 1 and t > 0:
             self.dec.reorder(self.src_s, t)
         cur_len = t + 1
-        forced = self.forced_eos if (self.forced_eos is not None and cur_len == self.max_length - 1) else -1
-        if self.forced_bos is not None and cur_len == 1:             # ForcedBOSTokenLogitsProcessor (runs before ForcedEOS in HF)
-            forced = self.forced_bos if forced < 0 else forced
+        forced = self.forced_at(cur_len)
         V = self.model.V
         pen = {}
         if self.pen_rule:
@@ -506,7 +522,12 @@ class DecodeSession:
                                  suppress_eos=cur_len < self.min_length, forced_token=forced, **pen)
         if self.beam is not None:
             from . import _lib
-            _lib.check(_lib.lib.vacnic_beam_step(_lib.C.byref(self.beam), tv.data_ptr(), ti.data_ptr(), tv.shape[1], cur_len, K._stream()))
+            if self.groups:
+                ga = K.group_beam_args(self.groups, forced, self.penalty, self.pen_rule)
+                _lib.check(_lib.lib.vacnic_group_beam_step(_lib.C.byref(self.beam), _lib.C.byref(ga), tv.data_ptr(), ti.data_ptr(), tv.shape[1],
+                                                           cur_len, K._stream()))
+            else:
+                _lib.check(_lib.lib.vacnic_beam_step(_lib.C.byref(self.beam), tv.data_ptr(), ti.data_ptr(), tv.shape[1], cur_len, K._stream()))
         return tv, ti
 
     def step(self, t, last_tokens, scores, src, bans, use_graphs, seqs=None):
@@ -624,13 +645,59 @@ _DECODE_KEY_LEN = 9        # entries of a DecodeSession key without processors; 
 _PROCESSOR_SESSIONS_MAX = 8   # beam / greedy sessions with processors a model keeps (each holds a KV cache and position graphs)
 
 
-def _decode_session_key(R, S, max_length, nb, ngram, min_length, forced_eos, forced_bos, beams, bad_words, penalty):
+def _decode_session_key(R, S, max_length, nb, ngram, min_length, forced_eos, forced_bos, beams, bad_words, penalty, groups=None):
     """what a DecodeSession is kept under: the shape and the options baked into its launches; the processors join it only when one
-    is on (the penalty as the float32 the kernels see), so that the default key is the one of before"""
+    is on (the penalty as the float32 the kernels see), and (num_beam_groups, diversity_penalty as float32) only with more than one
+    group, so that the default key is the one of before"""
     key = (R, S, max_length, nb, ngram, min_length, forced_eos, forced_bos, beams)
     if bad_words or penalty != 1.0:
         key = key + (bad_words, penalty)
+    if groups and groups[0] > 1:
+        key = key + (int(groups[0]), _f32(groups[1]))
     return key
+
+
+def _check_group_args(num_beams, num_beam_groups, diversity_penalty, do_sample, encoded):
+    """the checks of transformers 4.18 on num_beam_groups / diversity_penalty, plus this library's: a diversity penalty without groups
+    is an error here (HF ignores it), and groups do not combine with staged encoding.  Returns (G, penalty as float32)."""
+    G, lam = num_beam_groups, diversity_penalty
+    if isinstance(G, bool) or not isinstance(G, int) or G < 1:
+        raise ValueError(f"`num_beam_groups` has to be an integer >= 1, but is {G!r}")
+    ok = isinstance(lam, numbers.Real) and not isinstance(lam, bool)
+    if ok:
+        ok = 0.0 <= _f32(lam) < float("inf")
+    if not ok:
+        raise ValueError(f"`diversity_penalty` has to be a finite float >= 0 (as float32), but is {lam!r}")
+    if G > num_beams:
+        raise ValueError("`num_beam_groups` has to be smaller or equal to `num_beams`")
+    if num_beams % G != 0:
+        raise ValueError("`num_beams` should be divisible by `num_beam_groups`")
+    if G > 1 and do_sample:
+        raise ValueError("Diverse beam search cannot be used in sampling mode. Make sure that `do_sample` is set to `False`.")
+    if G == 1 and _f32(lam) != 0.0:
+        raise ValueError(f"`diversity_penalty` = {lam!r} needs `num_beam_groups` > 1 (it would be ignored: pass 0.0 or ask for groups)")
+    if G > 1 and encoded is not None:
+        raise ValueError("generate(encoded=...): staged encoding is not supported with `num_beam_groups` > 1")
+    return G, _f32(lam)
+
+
+def nbest_to_sequences(nbest, n, pad, eos, max_length):
+    """the n best hypotheses of every item of a return_nbest list as BeamSearchScorer.finalize(num_beam_hyps_to_keep=n) of transformers
+    4.18 lays them out: int64 [B * n, L] (row b * n + j = the j-th best of item b; its ids, eos behind a hypothesis shorter than L, then
+    pad) and the float32 scores [B * n]; L = min(longest + 1, max_length).  The n-best list of a (diverse) beam search goes through
+    this into training.sequences_to_labels -> model.score."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"nbest_to_sequences: n has to be an integer >= 1, but is {n!r}")
+    if any(len(item) < n for item in nbest):
+        raise ValueError(f"nbest_to_sequences: n = {n}, but an item has only {min(len(item) for item in nbest)} hypotheses")
+    rows = [(sc, sq) for item in nbest for sc, sq in item[:n]]
+    L = min(max(len(sq) for _, sq in rows) + 1, max_length)
+    ids = torch.full((len(rows), L), pad, dtype=torch.long)
+    for r, (_, sq) in enumerate(rows):
+        ids[r, :len(sq)] = torch.tensor(sq, dtype=torch.long)
+        if len(sq) < L:
+            ids[r, len(sq)] = eos
+    return ids, torch.tensor([sc for sc, _ in rows], dtype=torch.float32)
 
 
 def _sample_session_key(R, S, max_length, ngram, min_length, forced_eos, forced_bos, bad_words):
@@ -774,7 +841,8 @@ class CaptionPipeline:
         """stage B (encoder stream): encoder + cross K/V of one caption into the EncodeStage, not before `after` (the previous caption's
         staged data have been copied into the decoder's buffers)"""
         src, src_mask, feats, kw = ent["inputs"]
-        if src.shape[0] != 1 or self.gen_kw.get("do_sample"):          # (sampling decodes through the plain generate(): no staging)
+        # (sampling and group beam search decode through the plain generate(): no staging)
+        if src.shape[0] != 1 or self.gen_kw.get("do_sample") or self.gen_kw.get("num_beam_groups", 1) != 1:
             return
         with torch.cuda.stream(self.s_enc):
             self.s_enc.wait_event(ent["a"])
@@ -838,7 +906,8 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
              no_repeat_ngram_size=0, min_length=0, forced_eos_token_id="config", forced_bos_token_id=None, image_features=None,
              face_features=None, face_mask=None, name_ids=None, name_mask=None, add_ner_ffn=True, use_graphs=True, device_beams=True,
              return_nbest=False, encoded=None, _after_begin=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0,
-             num_return_sequences=1, seed=None, return_logprobs=False, repetition_penalty=1.0, bad_words_ids=None, **unused):
+             num_return_sequences=1, seed=None, return_logprobs=False, repetition_penalty=1.0, bad_words_ids=None, num_beam_groups=1,
+             diversity_penalty=0.0, **unused):
     """GenerationMixin.generate(do_sample=False) semantics of transformers 4.18 for this model (greedy = 1 beam).
     Returns int64 [B, L] starting with decoder_start_token_id, padded with pad_token_id.
     Keyword defaults are the LIBRARY defaults; the defaults a hub checkpoint's config.json adds on top (what the reference's
@@ -858,7 +927,14 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
     bad_words_ids (NoBadWordsLogitsProcessor of 4.18; every path): a list of token-id lists that must not be generated; [eos] is
     dropped, at most kernels.BAD_WORDS_MAX words of kernels.BAD_WORD_LEN tokens.  repetition_penalty (a finite number > 0, below 1
     rewards repetition; RepetitionPenaltyLogitsProcessor): on the raw logits with do_sample=True and with one beam, on the
-    log-softmax scores with more beams, as HF's sample / greedy_search / beam_search apply it (include/vacnic_hip.h has the rules)."""
+    log-softmax scores with more beams, as HF's sample / greedy_search / beam_search apply it (include/vacnic_hip.h has the rules).
+
+    num_beam_groups=G > 1, diversity_penalty: group (diverse) beam search, 4.18's group_beam_search with HammingDiversityLogitsProcessor:
+    the beams of an item are G groups of num_beams / G, handled in order at every position; a token that f beams of the earlier groups
+    chose in this position scores diversity_penalty * f less (include/vacnic_hip.h at vacnic_group_beam_step has the exact rules).  One
+    n-best list per item, shared by its groups: return_nbest / nbest_to_sequences hand out the diverse candidates.  With G == 1 (the
+    default; diversity_penalty must then be 0) the call is the one of before."""
+    _check_group_args(num_beams, num_beam_groups, diversity_penalty, do_sample, encoded)
     if do_sample:
         _check_sampling_args(num_beams, encoded, temperature, top_k, top_p, num_return_sequences)
     bad_words = None
@@ -898,8 +974,11 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
         S, d = enc_h.shape[1], enc_h.shape[2]
     device_beams = bool(device_beams) and nb <= 16 and 2 * nb * nb <= 128 and max_length <= 512
     penalty = _f32(repetition_penalty)                   # the value the kernels see: 1 + 1e-12 is "off"
+    groups = (num_beam_groups, _f32(diversity_penalty)) if num_beam_groups > 1 else None
+    G = num_beam_groups
+    gs = nb // G                                         # beams per group (all of them without groups)
     key = _decode_session_key(R, S, max_length, nb, no_repeat_ngram_size, min_length, forced_eos_token_id, forced_bos_token_id,
-                              (float(length_penalty), bool(early_stopping)) if device_beams else None, bad_words, penalty)
+                              (float(length_penalty), bool(early_stopping)) if device_beams else None, bad_words, penalty, groups)
     processors = len(key) > _DECODE_KEY_LEN
     sessions = model.__dict__.setdefault("_decode_sessions", {})
     ses = sessions.get(key)
@@ -913,7 +992,7 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
             for k in keyed[:max(0, len(keyed) - _PROCESSOR_SESSIONS_MAX + 1)]:
                 del sessions[k]
         ses = sessions[key] = DecodeSession(model, R, S, max_length, nb, no_repeat_ngram_size, min_length, forced_eos_token_id, eos,
-                                            forced_bos=forced_bos_token_id, bad_words=bad_words, penalty=penalty)
+                                            forced_bos=forced_bos_token_id, bad_words=bad_words, penalty=penalty, groups=groups)
         if device_beams:
             ses.enable_device_beams(B, length_penalty, early_stopping, pad)
     if encoded is not None:
@@ -956,11 +1035,13 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
         return (res.to(dev), nbest) if return_nbest else res.to(dev)
 
     seqs = [[start] for _ in range(R)]
-    beam_scores = [0.0 if (r % nb) == 0 else -1e9 for r in range(R)]
+    beam_scores = [0.0 if (r % gs) == 0 else -1e9 for r in range(R)]    # the first beam of every group is live
     hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(B)]
     done = [False] * B
     cur_len = 1
-    Kc = 2 * nb
+    Kc = 2 * gs
+    lam = groups[1] if groups else 0.0
+    pen_scores = penalty if ses.pen_rule == "scores" else 1.0
     new_src = list(range(R))
     while True:
         t = cur_len - 1
@@ -976,35 +1057,48 @@ def generate(model, input_ids=None, attention_mask=None, num_beams=1, max_length
             raise
         tv, ti = tv.tolist(), ti.tolist()
         new_seqs, new_scores, new_src = [], [], []
-        for b in range(B):
-            if done[b]:
-                new_seqs += [seqs[b * nb] + [pad]] * nb; new_scores += [0.0] * nb; new_src += [b * nb] * nb
+        hamming = groups is not None and ses.forced_at(cur_len) < 0      # a forced position overwrites the Hamming term (HF's order)
+        for b, g in ((b, g) for b in range(B) for g in range(G)):
+            # the groups of an item in order (one group = ordinary beam search); new_tok: the tokens its earlier groups chose here
+            r0 = b * nb + g * gs
+            if g == 0:
+                new_tok = []
+            if done[b]:                                                 # on entry, or by an earlier group of this position
+                new_seqs += [seqs[r0] + [pad]] * gs; new_scores += [0.0] * gs; new_src += [r0] * gs
                 continue
-            # merge the per-beam top-2k lists into the group's top-2k (HF: topk over the [nb*V] scores of the group)
+            # merge the per-beam top-2k lists into the group's top-2k (HF: topk over the [gs*V] scores of the group)
             cand = []
-            for j in range(nb):
-                row_v, row_i = tv[b * nb + j], ti[b * nb + j]
+            for j in range(gs):
+                row_v, row_i = tv[r0 + j], ti[r0 + j]
                 for c in range(len(row_v)):
                     if row_i[c] >= 0:
-                        cand.append((row_v[c], j, row_i[c]))
+                        sc = row_v[c]
+                        f = new_tok.count(row_i[c]) if (hamming and g > 0) else 0
+                        if f > 0:
+                            # vacnic_group_beam_step's Hamming term, rounded as the kernel rounds it: lambda f [P inside the history]
+                            h = _f32(lam * f)
+                            if pen_scores != 1.0 and row_i[c] in seqs[r0 + j]:
+                                h = _f32(h * pen_scores)
+                            sc = _f32(sc - h)
+                        cand.append((sc, j, row_i[c]))
             cand.sort(key=lambda x: (-x[0], x[1] * model.V + x[2]))
             cand = cand[:Kc]
             chosen = []
             for rank, (sc, j, tok) in enumerate(cand):
-                src = b * nb + j
+                src = r0 + j
                 if tok == eos:
-                    if rank >= nb:
+                    if rank >= gs:
                         continue
                     hyps[b].add(seqs[src], sc)
                 else:
                     chosen.append((sc, tok, src))
-                if len(chosen) == nb:
+                if len(chosen) == gs:
                     break
             done[b] = done[b] or hyps[b].is_done(cand[0][0], cur_len)
-            while len(chosen) < nb:                                     # cannot happen with 2*nb candidates; keep shapes sane
-                chosen.append((-1e9, pad, b * nb))
+            while len(chosen) < gs:                                     # cannot happen with 2*gs candidates; keep shapes sane
+                chosen.append((-1e9, pad, r0))
             for sc, tok, src in chosen:
-                new_seqs.append(seqs[src] + [tok]); new_scores.append(sc); new_src.append(src)
+                new_seqs.append(seqs[src] + [tok]); new_scores.append(sc); new_src.append(src); new_tok.append(tok)
         seqs = new_seqs
         beam_scores = new_scores
         cur_len += 1

@@ -1141,10 +1141,23 @@ def gather_rows(src, dst, idx, rows, row_bytes, row_stride_bytes=0, period=0):
     call("vacnic_gather_rows", _p(src), _p(dst), _p(idx), rows, row_bytes, row_stride_bytes, period, _stream())
 
 
-def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=False, length_penalty=1.0, device="cuda", bad_words=None):
+def group_beam_args(groups, forced_token=-1, repetition_penalty=1.0, penalty_rule=None):
+    """vacnic_group_beam_args from groups = (num_beam_groups, diversity_penalty) and the processors of the position's top-k call"""
+    if penalty_rule == "logits":
+        raise ValueError("group beam search: the repetition penalty is on the scores (more than one beam), never on the logits")
+    return _lib.GroupBeamArgs(num_beam_groups=int(groups[0]), diversity_penalty=float(groups[1]), repetition_penalty=float(repetition_penalty),
+                              penalty_rule=PENALTY_RULES[penalty_rule], forced_token=int(forced_token))
+
+
+def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=False, length_penalty=1.0, device="cuda", bad_words=None,
+               groups=None):
     """the device state of vacnic_beam_init / vacnic_beam_step (include/vacnic_hip.h) as a namespace of tensors + the C struct `st`.
-    bad_words: (table, lengths) from bad_words_table; the ban lists are then Lmax + n_bad wide."""
+    bad_words: (table, lengths) from bad_words_table; the ban lists are then Lmax + n_bad wide.
+    groups = (num_beam_groups, diversity_penalty): the same state serves vacnic_group_beam_init / vacnic_group_beam_step (group_beam_init /
+    group_beam_step below read it from `s.groups`); None = ordinary beams."""
     import types
+    if groups is not None and (int(groups[0]) < 1 or nb % int(groups[0]) != 0):
+        raise ValueError(f"beam_alloc: num_beam_groups {groups[0]} must be >= 1 and divide nb = {nb}")
     R = B * nb
     n_bad = 0 if bad_words is None else int(bad_words[1].shape[0])
     bw = {} if bad_words is None else dict(bad_words=_p(bad_words[0]), bad_len=_p(bad_words[1]), n_bad=n_bad)
@@ -1161,6 +1174,7 @@ def beam_alloc(B, nb, Lmax, V, eos, pad, no_repeat_ngram_size=0, early_stopping=
                           hyp_seq=_p(s.hyp_seq), next_ids=_p(s.next_ids), src_idx=_p(s.src_idx), bans=_p(s.bans), B=B, nb=nb, Lmax=Lmax,
                           V=V, eos=eos, pad=pad, no_repeat_ngram_size=no_repeat_ngram_size, early_stopping=int(bool(early_stopping)),
                           length_penalty=float(length_penalty), **bw)
+    s.groups = None if groups is None else (int(groups[0]), float(groups[1]))
     return s
 
 
@@ -1171,3 +1185,16 @@ def beam_init(state, start_token):
 def beam_step(state, top_val, top_idx, cur_len):
     """one position of the on-device beam bookkeeping: top_val f32 / top_idx int32 [B * nb, K2] from beam_topk / lmhead_topk."""
     call("vacnic_beam_step", _lib.C.byref(state.st), _p(top_val), _p(top_idx), top_val.shape[1], int(cur_len), _stream())
+
+
+def group_beam_init(state, start_token, groups=None):
+    """vacnic_group_beam_init on a beam_alloc state: slot 0 of every group starts live (groups defaults to the state's own)"""
+    ga = group_beam_args(groups or state.groups or (1, 0.0))
+    call("vacnic_group_beam_init", _lib.C.byref(state.st), _lib.C.byref(ga), int(start_token), _stream())
+
+
+def group_beam_step(state, top_val, top_idx, cur_len, groups=None, forced_token=-1, repetition_penalty=1.0, penalty_rule=None):
+    """one position of group (diverse) beam search bookkeeping; forced_token / repetition_penalty / penalty_rule: those of the top-k
+    call that produced top_val / top_idx (the Hamming term skips a forced position and carries the penalty's factor)."""
+    ga = group_beam_args(groups or state.groups or (1, 0.0), forced_token, repetition_penalty, penalty_rule)
+    call("vacnic_group_beam_step", _lib.C.byref(state.st), _lib.C.byref(ga), _p(top_val), _p(top_idx), top_val.shape[1], int(cur_len), _stream())
