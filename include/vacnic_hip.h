@@ -169,7 +169,9 @@ int vacnic_wgrad_group(const vacnic_wgrad_job* jobs, int64_t njobs, void* stream
  *             (MFULL:387-398) does (an all-masked row therefore softmaxes uniformly, like torch).
  *   causal:   1 => key j masked for query i when j > i (MFULL:373-385).
  *   scale:    multiplies q.k (reference multiplies q by head_dim**-0.5, MFULL:471).
- *   lse:      f32 [B][H][Tq] log-sum-exp of the scaled+masked scores (saved for backward).
+ *   lse:      f32 [B][H][Tq] log-sum-exp of the scaled+masked scores (saved for backward); finfo(float32).min for a query whose
+ *             keys are all masked (an empty batch row), which vacnic_attn_bwd reads as "softmaxed uniformly".
+ *   Tk <= 8192 (VACNIC_UNSUPPORTED beyond: the key bias of a row lives in LDS).
  */
 typedef struct {
   const void* q; const void* k; const void* v; void* out; float* lse;

@@ -20,6 +20,11 @@ namespace {
 constexpr float FMIN = -3.4028234663852886e38f;
 constexpr int OOB = 0x7ffffff0;
 constexpr int TILE_B = 64 * 64 * 2;   // one [64][64] bf16 tile = 8 KiB
+// The forward and dQ kernels keep the key bias of the whole key range in LDS next to the K/V ring: 32 KiB + 4 Tk_pad + Tk_pad / 16
+// bytes.  That is 65,528 at Tk_pad = 8064 and passes 64 KiB beyond it (66,048 at TK_MAX), so their launches declare LONG_LDS_MAX
+// (hipFuncAttributeMaxDynamicSharedMemorySize) like the one-kernel backward does for its 66 KiB; two workgroups still fit a CU.
+constexpr int TK_MAX = 8192;
+constexpr int LONG_LDS_MAX = 4 * TILE_B + TK_MAX * 4 + (TK_MAX >> 6) * 4;
 
 __device__ __forceinline__ int swz(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
 
@@ -361,7 +366,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
       if (qrow < p.Tq) *(u32x4*)(p.out + (long)b * p.bso + (long)qrow * p.ldo + hd * 64 + c16 * 8) = v;
     }
   }
-  if (qidx < p.Tq && p.lse && hh == 0) p.lse[((long)b * p.H + hd) * p.Tq + qidx] = m_run * 0.6931471805599453f + __logf(l_tot);
+  // A row whose visible keys are all masked (an empty batch row) ends with m_run == FMIN exactly: every finite score was absorbed.
+  // The additive mask is FMIN in the natural-log domain of lse as well (it is not a score to be scaled by ln 2), so that row's lse
+  // is FMIN + log(count) = FMIN, as torch's logsumexp gives it and as the backward kernels recognise it.
+  if (qidx < p.Tq && p.lse && hh == 0)
+    p.lse[((long)b * p.H + hd) * p.Tq + qidx] = (m_run == FMIN ? FMIN : m_run * 0.6931471805599453f) + __logf(l_tot);
 }
 
 // A wave's 32 x 64 gradient tile (two 32x32 accumulators, the row on the lane) leaves as whole rows, the way the forward's output
@@ -537,7 +546,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnP p) {
           for (int e = 0; e < 4; ++e) {
             float v = s[4 * g + e] * p.scale + kbias;
             if (p.causal && kidx > (t * 64 + ql0 + e)) v += FMIN;
-            const float pe = __expf(v - l4[e]);
+            const float pe = __expf(v - l4[e]);            // (an empty batch row: 1, not 1 / Tk — see uniform_w below)
             s[4 * g + e] = DROP ? pe * mq[e] : pe;
             dp[4 * g + e] = pe * ((DROP ? dp[4 * g + e] * mq[e] : dp[4 * g + e]) - d4[e]);
           }
@@ -556,14 +565,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnP p) {
     lds_barrier();
   }
 
+  // An empty batch row (every key masked, no causal flag) was softmaxed uniformly by the forward, but the lse of its queries is
+  // FMIN with log(Tk) absorbed: exp(score - lse) above gave 1 for every key (FMIN - FMIN; 0 for the padding), not 1 / Tk.  This
+  // workgroup sees only its own 128 keys, but the lse says so, and it says the same of every query of the (batch, head): P and
+  // dS = P o (dP - delta) are Tk times the uniform softmax's for all of them (delta is right: it comes from O, or from the dQ
+  // sweep, which knows), so dK and dV are, and 1 / Tk goes into the scale on the way out — the loop stays as it is.  With the
+  // causal flag the count differs from query to query; a key mask that empties a row together with the causal flag is not served.
+  const float uniform_w = (!p.causal && lse[0] == FMIN) ? 1.f / (float)p.Tk : 1.f;      // (1 otherwise: the scales below are exact)
+  const float sc_k = p.scale * uniform_w;
   // The Q / dO ring is idle behind the loop's last barrier: each wave turns dK and dV round in 2 x 4 KiB of it (store_rows32).
   // Unaligned dk / dv take the accumulator layout's own 8-byte pieces.
   if (p.rows16) {
     if (k0 < p.Tk) {
       char* ot = smem + wave * 8192;
-      // (dV carries no scale: * 1.f is exact)
-      store_rows32(ot, dk, p.scale, p.dk + (long)b * p.bsdk + (long)k0 * p.lddk + hd * 64, p.lddk, k0, p.Tk, lane);
-      store_rows32(ot + 4096, dv, 1.f, p.dv + (long)b * p.bsdv + (long)k0 * p.lddv + hd * 64, p.lddv, k0, p.Tk, lane);
+      // (dV carries no scale but uniform_w: * 1.f is exact)
+      store_rows32(ot, dk, sc_k, p.dk + (long)b * p.bsdk + (long)k0 * p.lddk + hd * 64, p.lddk, k0, p.Tk, lane);
+      store_rows32(ot + 4096, dv, uniform_w, p.dv + (long)b * p.bsdv + (long)k0 * p.lddv + hd * 64, p.lddv, k0, p.Tk, lane);
     }
   } else if (kidx < p.Tk) {
     bf16_t* dkrow = p.dk + (long)b * p.bsdk + (long)kidx * p.lddk + hd * 64;
@@ -572,8 +589,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(AttnP p) {
     for (int hb = 0; hb < 2; ++hb)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        u32x2 a = {pack2bf(dk[hb][4 * g] * p.scale, dk[hb][4 * g + 1] * p.scale), pack2bf(dk[hb][4 * g + 2] * p.scale, dk[hb][4 * g + 3] * p.scale)};
-        u32x2 c = {pack2bf(dv[hb][4 * g], dv[hb][4 * g + 1]), pack2bf(dv[hb][4 * g + 2], dv[hb][4 * g + 3])};
+        u32x2 a = {pack2bf(dk[hb][4 * g] * sc_k, dk[hb][4 * g + 1] * sc_k), pack2bf(dk[hb][4 * g + 2] * sc_k, dk[hb][4 * g + 3] * sc_k)};
+        u32x2 c = {pack2bf(dv[hb][4 * g] * uniform_w, dv[hb][4 * g + 1] * uniform_w), pack2bf(dv[hb][4 * g + 2] * uniform_w, dv[hb][4 * g + 3] * uniform_w)};
         *(u32x2*)(dkrow + hb * 32 + 8 * g + 4 * hh) = a;
         *(u32x2*)(dvrow + hb * 32 + 8 * g + 4 * hh) = c;
       }
@@ -634,6 +651,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     if (!DELTA_PASS) delta_q = p.delta[((long)b * p.H + hd) * p.Tq + qidx];
   }
   const float nl2 = -lse_q * LOG2E;                    // (padding queries: -inf -> probability 0)
+  // A query whose visible keys are ALL masked (every query of an empty batch row) was softmaxed uniformly by the forward, but its
+  // lse is FMIN with log(count) absorbed: exp(score - lse) below gives 1 for each of its count keys (FMIN - FMIN) and 0 for the
+  // others (-inf), not 1 / count.  The query is on the lane, so 1 / count is one factor of its whole row of P and of dS: it
+  // multiplies delta and dQ on the way out and the loops stay as they are.  (Every tile of such a row is dirty: never plain.)
+  const float w_q = lse_q == FMIN ? 1.f / (float)(p.causal ? min(qidx, p.Tk - 1) + 1 : p.Tk) : 1.f;
   float dsum = 0.f;
   f32x16 dq[2];
   dq[0] = (f32x16)(0.f); dq[1] = (f32x16)(0.f);
@@ -705,19 +727,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   }
   if (DELTA_PASS) {
     dsum += __shfl_xor(dsum, 32, 64);                         // the two lane halves hold different keys of the same query
-    if (qidx < p.Tq && hh == 0) p.delta_out[((long)b * p.H + hd) * p.Tq + qidx] = dsum;
+    if (qidx < p.Tq && hh == 0) p.delta_out[((long)b * p.H + hd) * p.Tq + qidx] = dsum * w_q;
     return;
   }
+  const float sc_q = p.scale * w_q;                        // (w_q == 1 but for the uniform rows: exactly p.scale)
   if (p.rows16) {                                          // whole rows through the idle K/V ring, as in the dK/dV kernel
-    if (q0 < p.Tq)
-      store_rows32(smem + wave * 4096, dq, p.scale, p.dq + (long)b * p.bsdq + (long)q0 * p.lddq + hd * 64, p.lddq, q0, p.Tq, lane);
+    if (q0 < p.Tq)                                         // (store_rows32 scales row lane & 31 = this lane's query)
+      store_rows32(smem + wave * 4096, dq, sc_q, p.dq + (long)b * p.bsdq + (long)q0 * p.lddq + hd * 64, p.lddq, q0, p.Tq, lane);
   } else if (qidx < p.Tq) {
     bf16_t* drow = p.dq + (long)b * p.bsdq + (long)qidx * p.lddq + hd * 64;
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        u32x2 a = {pack2bf(dq[hb][4 * g] * p.scale, dq[hb][4 * g + 1] * p.scale), pack2bf(dq[hb][4 * g + 2] * p.scale, dq[hb][4 * g + 3] * p.scale)};
+        u32x2 a = {pack2bf(dq[hb][4 * g] * sc_q, dq[hb][4 * g + 1] * sc_q), pack2bf(dq[hb][4 * g + 2] * sc_q, dq[hb][4 * g + 3] * sc_q)};
         *(u32x2*)(drow + hb * 32 + 8 * g + 4 * hh) = a;
       }
   }
@@ -1071,7 +1094,7 @@ int check_common(int64_t B, int64_t H, int64_t Tq, int64_t Tk, int64_t ldq, int6
     vacnic_set_error("%s: row strides must be multiples of 8 elements", who);
     return VACNIC_MISALIGNED;
   }
-  if (Tk > 8192 || H > 65535 || B > 65535) {
+  if (Tk > TK_MAX || H > 65535 || B > 65535) {
     vacnic_set_error("%s: Tk=%ld / H / B beyond supported range", who, (long)Tk);
     return VACNIC_UNSUPPORTED;
   }
@@ -1231,6 +1254,16 @@ extern "C" int vacnic_attn_fwd(const vacnic_attn_fwd_args* a, void* stream) {
   dim3 grid((unsigned)(((p.Tq + 127) / 128) * p.H * p.B));
   const size_t lds = 4 * TILE_B + Tk_pad * 4 + (Tk_pad >> 6) * 4;          // K/V ring + key bias + per-tile flags
   hipStream_t st = (hipStream_t)stream;
+  {
+    static bool once = false;                          // up to LONG_LDS_MAX > 64 KiB of dynamic LDS: every instantiation is told so once
+    if (!once) {
+      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      once = true;
+    }
+  }
   if (p.drop_thr) {
     if (p.causal) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), lds, st, p);
     else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), lds, st, p);
@@ -1281,6 +1314,16 @@ extern "C" int vacnic_attn_bwd(const vacnic_attn_bwd_args* a, void* stream) {
     else hipLaunchKernelGGL(attn_bwd_short_kernel<false>, gbh, dim3(256), SHORT_LDS, s, p);
     VLAUNCH_CHECK();
     return VACNIC_OK;
+  }
+  {
+    static bool once = false;                          // up to LONG_LDS_MAX > 64 KiB of dynamic LDS, as in attn_fwd
+    if (!once) {
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LONG_LDS_MAX);
+      once = true;
+    }
   }
   // delta: from the kernels' own P and dP (a sweep of the dQ kernel without its last product) for the decoder-sized problems,
   // where it costs microseconds; rowsum(dO o O) for the long encoder sequences
